@@ -11,9 +11,16 @@ contiguous chunks (8/N frames per GPU); the exchange is RCCL send/recv issued by
 stream (fallbacks: torch.distributed point-to-point, then broadcast). Inputs are resident in HBM when the
 timed region starts.
 
-At N = 1 the same run also times BASELINE config 2 (one frame, no temporal filter) and reports it as
-`config2_single_frame`, next to `roofline` (dominant kernel = level-0 ping-pong; the kernel is bound by
-VALU issue, not HBM — see DESIGN.md §6) and `cpu_baseline` (the CPU oracle on the host cores).
+A plain run sets up, warms up, times --steps steps and prints the headline figure. With --full the timed
+steps also record per-stage spans, and the line adds `roofline` (dominant kernel = level-0 ping-pong; the
+kernel is bound by VALU issue, not HBM — see DESIGN.md §6), the per-stage / per-level times, the halo
+exchange statistics and `result_crc` (checked against tests/golden/bench_result_crc.json); at N = 1 it then
+also times BASELINE config 2 (one frame, no temporal filter) as `config2_single_frame` and runs
+`cpu_baseline` (the CPU oracle on the host cores).
+
+--dump-outputs DIR writes what the last timed step computed: every frame's level-0 disparity (all
+destinations), as DIR/disparity_frame<t>.npy with its field-of-view mask DIR/fov_mask_frame<t>.npy (float32,
+finite: see dump_outputs), a fixed seeded sample of them when the whole would exceed DUMP_BYTES (see dump_index).
 
 Prints ONE JSON line on rank 0 (driver contract in the task statement).
 """
@@ -31,6 +38,8 @@ HBM_PEAK_GBS = 8000.0
 N_SIMD = 256 * 4
 PEAK_CLOCK_GHZ = 2.4
 VALU_PEAK_GCYC = N_SIMD * PEAK_CLOCK_GHZ  # SIMD-cycles available per second (x 1e9)
+DUMP_BYTES = 64 * 10**6  # all files --dump-outputs writes, together
+DUMP_SEED = 360
 
 
 def parse():
@@ -38,6 +47,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: per-stage spans, roofline, "
+                         "result_crc, halo exchange statistics, and at N = 1 the config-2 single-frame leg and the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the level-0 disparity the last timed step computed, as DIR/disparity_frame<t>.npy")
     ap.add_argument("--config", default="cfg2", help="rig: cfg1 | cfg2 | cfg4 | small | tiny (default: BASELINE config 2/3's rig)")
     ap.add_argument("--frames", type=int, default=8, help="frames of the sequence (BASELINE config 3: 8)")
     ap.add_argument("--temporal", type=int, default=1, help="0 = no temporal filter (frames are then independent replicas)")
@@ -45,12 +60,12 @@ def parse():
     ap.add_argument("--synth-device", default="cuda",
                     help="where the synthetic frames are rendered: cuda (default, fast) | cpu (bit-identical to the frames "
                          "the CPU tests render, so result_crc can be compared with the oracle's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "full", "sample"],
-                    help="the CPU oracle on frame 0 of the workload: full = every level measured (about 2.5 minutes for "
+                    help="with --full, the CPU oracle on frame 0 of the workload: full = every level measured (about 2.5 minutes for "
                          "16 x 2048^2 on 16 CPUs), sample = levels 9..2 measured and levels 1-0 extrapolated by pixel "
                          "count (about 10 s), auto = full when this process may use >= 16 CPUs")
-    ap.add_argument("--no-single-frame", action="store_true", help="skip the config-2 single-frame leg at N = 1")
+    ap.add_argument("--no-single-frame", action="store_true", help="with --full: skip the config-2 single-frame leg at N = 1")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--exchange", default="rccl,torch,broadcast",
                     help="transports to try for the halo exchange, in order")
@@ -177,6 +192,46 @@ def cpu_baseline(rig, sizes, frame, res, n_cams, mode="auto"):
     return out
 
 
+def dump_index(n_values, n_frames):
+    """Which of a frame's `n_values` level-0 disparities --dump-outputs writes: None = all of them, when every frame's
+    two files (disparity and FOV mask, float32) fit in DUMP_BYTES; otherwise the same sorted sample for every frame,
+    drawn from a fixed seed, sized so that the frames' files and the index file (float64) fit together."""
+    import numpy as np
+
+    header = 128  # bytes of an .npy header
+    if n_frames * 2 * (4 * n_values + header) <= DUMP_BYTES:
+        return None
+    n = (DUMP_BYTES - (2 * n_frames + 1) * header) // (8 * n_frames + 8)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_values, n, dtype=np.int64))
+
+
+def dump_outputs(path, runner, n_frames, rank):
+    """--dump-outputs: every owned frame's level-0 disparity after the last timed step, destinations in rig order, as
+    path/disparity_frame<t>.npy (float32: D x H x W, or the dump_index sample of the flattened D x H x W values, whose
+    positions rank 0 writes to path/disparity_sample_index.npy). The library writes NaN where a destination's pixel lies
+    outside its field of view; the files hold only finite values, so such a pixel is written as 0 in the disparity and
+    as 0 in path/fov_mask_frame<t>.npy (same shape, 1 = the disparity is a number)."""
+    import numpy as np
+
+    g = runner.g
+    w, h = g.sizes[0]
+    idx = dump_index(g.D * w * h, n_frames)
+    os.makedirs(path, exist_ok=True)
+    if idx is not None:
+        bounds = np.searchsorted(idx, np.arange(g.D + 1) * (w * h))
+        if rank == 0:
+            np.save(os.path.join(path, "disparity_sample_index.npy"), idx.astype(np.float64))
+    for t in runner.owned:
+        planes = []
+        for d in range(g.D):
+            plane = runner.download_disparity(t, 0, d)
+            planes.append(plane if idx is None else plane.ravel()[idx[bounds[d]:bounds[d + 1]] - d * w * h])
+        disp = np.stack(planes) if idx is None else np.concatenate(planes)
+        fov = np.isfinite(disp)
+        np.save(os.path.join(path, "disparity_frame%d.npy" % t), np.where(fov, disp, np.float32(0)))
+        np.save(os.path.join(path, "fov_mask_frame%d.npy" % t), fov.astype(np.float32))
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` started plainly (no launcher: RANK / WORLD_SIZE unset) with N > 1: start the N ranks
     here, one process per GPU — the environment `python -m torch.distributed.run --nproc-per-node N` would give them —
@@ -225,6 +280,8 @@ def main():
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL peer-memory handles need it here
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         return launch_ranks(args)
     # stdout carries the one JSON line and nothing else: whatever a library prints there (Gloo's "Rank 0 is connected"
@@ -299,10 +356,11 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    g.profile_reset()
-    g.profile_enable(True)
-    runner.stats_reset()
-    fence()
+    if args.full:  # per-stage spans and exchange statistics of the timed steps
+        g.profile_reset()
+        g.profile_enable(True)
+        runner.stats_reset()
+        fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -317,6 +375,62 @@ def main():
     w0, h0 = sizes[0]
     total_mpix = args.frames * args.steps * n_cams * w0 * h0 / 1e6  # every frame of the sequence, all ranks
     value = total_mpix / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, args.frames, rank)
+
+    frames_here = len(runner.owned)
+    out = {
+        "metric": "depth Mpix/s per GPU (full pyramid, 16-cam 2048^2 rig); % HBM-read roofline",
+        "value": round(value, 3),
+        "unit": "Mpix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32+f64",  # photometry in f32 over u16 texels; camera geometry in f64
+        "data": "synthetic",
+        "config": {
+            "workload": ("BASELINE config %s: %d-camera %dx%d synthetic rig, %d-frame sequence, full %d-level pyramid per "
+                         "frame, %s; the same sequence for every --gpus N (%s partition, %d frame(s) on this rank)"
+                         % ({"cfg2": "3" if args.frames > 1 else "2", "cfg4": "4", "cfg1": "1"}.get(args.config, args.config),
+                            n_cams, res, res, args.frames, n_levels,
+                            "per-level temporal filter (+-2 frames)" if temporal else "no temporal filter",
+                            args.partition, frames_here)),
+            "name": "cfg3" if (args.config == "cfg2" and args.frames == 8 and temporal) else args.config,
+            "rig": args.config,
+            "cameras": n_cams,
+            "resolution": [res, res],
+            "levels": [list(s) for s in sizes],
+            "frames": args.frames,
+            "temporal_filter": temporal,
+            "halo_transport": transport,
+            "warp_tables": ("cached across steps" if args.cache_warp_tables else
+                            "rebuilt once per level per step, shared by the frames of the level on a rank (rig-only data)"),
+            "parallelism": "frames x%d" % world,
+        },
+        "per_gpu_value": round(value / world, 3),
+        # SURVEY 8(d), for completeness: every pyramid level's pixels, not only the finest level's
+        "pyramid_value": round(value * sum(w * h for (w, h) in sizes) / (w0 * h0), 3),
+        "ms_per_frame": round(dt / args.steps / args.frames * 1e3 * world, 3),
+        "input_upload": {"bytes": upload_bytes, "seconds": round(upload_s, 3),
+                         "note": "host->HBM staging of this rank's colour pyramids, outside the timed region"},
+        "device": g.device_name(),
+    }
+
+    def finish():
+        runner.close()
+        g.close()
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
 
     # ---- per-rank measurements of the timed region
     pp = g.profile_query("ping_pong", 0)
@@ -454,44 +568,8 @@ def main():
             "frac_of_peak": round((whole_fetch + whole_write) / step_s / 1e9 / HBM_PEAK_GBS, 4),
             "compulsory_floor_bytes": floor_bytes}
 
-    frames_here = len(runner.owned)
-    out = {
-        "metric": "depth Mpix/s per GPU (full pyramid, 16-cam 2048^2 rig); % HBM-read roofline",
-        "value": round(value, 3),
-        "unit": "Mpix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32+f64",  # photometry in f32 over u16 texels; camera geometry in f64
-        "data": "synthetic",
-        "config": {
-            "workload": ("BASELINE config %s: %d-camera %dx%d synthetic rig, %d-frame sequence, full %d-level pyramid per "
-                         "frame, %s; the same sequence for every --gpus N (%s partition, %d frame(s) on this rank)"
-                         % ({"cfg2": "3" if args.frames > 1 else "2", "cfg4": "4", "cfg1": "1"}.get(args.config, args.config),
-                            n_cams, res, res, args.frames, n_levels,
-                            "per-level temporal filter (+-2 frames)" if temporal else "no temporal filter",
-                            args.partition, frames_here)),
-            "name": "cfg3" if (args.config == "cfg2" and args.frames == 8 and temporal) else args.config,
-            "rig": args.config,
-            "cameras": n_cams,
-            "resolution": [res, res],
-            "levels": [list(s) for s in sizes],
-            "frames": args.frames,
-            "temporal_filter": temporal,
-            "halo_transport": transport,
-            "halo_exchange": exch,
-            "warp_tables": ("cached across steps" if args.cache_warp_tables else
-                            "rebuilt once per level per step, shared by the frames of the level on a rank (rig-only data)"),
-            "parallelism": "frames x%d" % world,
-        },
-        "per_gpu_value": round(value / world, 3),
-        # SURVEY 8(d), for completeness: every pyramid level's pixels, not only the finest level's
-        "pyramid_value": round(value * sum(w * h for (w, h) in sizes) / (w0 * h0), 3),
-        "ms_per_frame": round(dt / args.steps / args.frames * 1e3 * world, 3),
+    out["config"]["halo_exchange"] = exch
+    out.update({
         "roofline": roofline,
         "stage_ms_per_step": stage_ms,
         "level_ms_per_frame": level_ms,  # all stages of one level of one frame (this rank), finest level first
@@ -501,10 +579,7 @@ def main():
         "result_crc": crc,
         "result_crc_matches_n1": crc_matches,
         "halo_transport_per_rank": transports,
-        "input_upload": {"bytes": upload_bytes, "seconds": round(upload_s, 3),
-                         "note": "host->HBM staging of this rank's colour pyramids, outside the timed region"},
-        "device": g.device_name(),
-    }
+    })
 
     if world == 1 and not args.no_single_frame:
         # BASELINE config 2: one frame (slot 0), no temporal filter — DerpCLI's own level loop
@@ -523,13 +598,7 @@ def main():
                         % (n_cams, res, res, n_levels)}
     if rank == 0 and world == 1 and not args.no_cpu_baseline and frame0 is not None:
         out["cpu_baseline"] = cpu_baseline(rig, sizes, frame0, res, n_cams, args.cpu_baseline)
-    runner.close()
-    g.close()
-    if rank == 0:
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if world > 1:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -44,8 +44,8 @@ def _line(p):
 
 
 def test_bench_single_process_small(built):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "small", "--frames", "4", "--steps", "1",
-                        "--warmup", "1", "--synth-device", "cpu"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "small", "--frames", "4",
+                        "--steps", "1", "--warmup", "1", "--synth-device", "cpu"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     out = _line(p)
     assert out["n_gpus"] == 1 and out["scaling"] == "strong" and out["unit"] == "Mpix/s" and out["value"] > 0
     assert out["config"]["frames"] == 4 and out["config"]["temporal_filter"] is True
@@ -63,6 +63,40 @@ def test_bench_single_process_small(built):
     assert out["result_crc"] == _oracle_crc_small(4) and out["halo_transport_per_rank"] == ["local"]
 
 
+def test_bench_plain_line_and_dumped_outputs(built, tmp_path):
+    """A plain run (no --full) prints the headline figure over exactly --steps timed steps and nothing that needs work
+    of its own; --dump-outputs writes what the last timed step computed: the CPU oracle's depth maps for this workload."""
+    import numpy as np
+
+    from facebook360_dep_amd import sequence, synth
+
+    dump = tmp_path / "outputs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "small", "--frames", "4", "--steps", "2",
+                        "--warmup", "1", "--synth-device", "cpu", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    out = _line(p)
+    assert out["unit"] == "Mpix/s" and out["higher_is_better"] is True and out["dtype"] == "f32+f64"
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["ms_per_step"] > 0
+    n, res, _ = synth.config("small")
+    # value = every frame's level-0 pixels of `steps` steps / their time, ms_per_step = that time / `steps`
+    assert abs(out["value"] * out["ms_per_step"] / (4 * n * res * res / 1e3) - 1) < 0.01
+    assert not {"roofline", "stage_ms_per_step", "result_crc", "config2_single_frame", "cpu_baseline"} & set(out)
+    crc = {}
+    for t in range(4):
+        a = np.load(dump / ("disparity_frame%d.npy" % t))
+        fov = np.load(dump / ("fov_mask_frame%d.npy" % t))
+        assert a.dtype == fov.dtype == np.float32 and a.shape == fov.shape == (n, res, res)
+        assert np.isfinite(a).all() and set(np.unique(fov)) <= {0.0, 1.0} and (a[fov == 0] == 0).all()
+        a = np.where(fov == 1, a, np.float32(np.nan))  # the library's NaN outside the field of view
+        c = 0
+        for d in range(n):
+            c = sequence.disparity_crc(a[d], c)
+        crc[str(t)] = "%08x" % c
+    assert crc == _oracle_crc_small(4)
+    assert sorted(f.name for f in dump.iterdir()) == sorted("%s_frame%d.npy" % (k, t) for k in ("disparity", "fov_mask")
+                                                            for t in range(4))
+
+
 def test_bench_two_ranks_one_gpu(built):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -70,7 +104,7 @@ def test_bench_two_ranks_one_gpu(built):
     env = dict(os.environ, DERP_BENCH_SINGLE_DEVICE="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small", "--frames", "4",
+                        "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small", "--frames", "4",
                         "--backend", "gloo", "--synth-device", "cpu"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     out = _line(p)
     assert out["n_gpus"] == 2 and out["config"]["frames"] == 4
@@ -90,7 +124,7 @@ def test_bench_plain_command_shards_itself_or_fails(built):
     than N devices it must FAIL, never print a 1-GPU line for a --gpus N request."""
     import torch
 
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small",
            "--frames", "4", "--backend", "gloo", "--synth-device", "cpu"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(env, DERP_BENCH_SINGLE_DEVICE="1"))

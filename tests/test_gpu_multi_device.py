@@ -141,7 +141,7 @@ def test_bench_two_gpus_over_rccl(built):
 
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small", "--frames", "4",
+                        "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "small", "--frames", "4",
                         "--synth-device", "cpu"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stderr[-3000:]
@@ -160,8 +160,8 @@ def test_bench_plain_command_two_gpus(built):
     """(e): `python bench.py --gpus 2` with no launcher — what the driver's scaling run types — starts its own two
     ranks, one per device, over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--config", "small", "--frames", "4", "--synth-device", "cpu"], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1",
+                        "--warmup", "1", "--config", "small", "--frames", "4", "--synth-device", "cpu"], capture_output=True, text=True,
                        timeout=900, cwd=ROOT, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -95,3 +95,21 @@ def test_bench_refuses_to_measure_fewer_gpus_than_asked():
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "tiny"],
                        capture_output=True, text=True, timeout=300, env=dict(env, RANK="0", WORLD_SIZE="1"))
     assert p.returncode != 0 and "does not match WORLD_SIZE" in p.stderr and "{" not in p.stdout
+
+
+def test_bench_dump_sample_fits_and_is_fixed(tmp_path):
+    """`bench.py --dump-outputs`: the default workload's level-0 disparity (8 frames x 16 x 2048^2 float32) is written as
+    one fixed, seeded sample per frame (disparity and FOV mask) plus its index, within 64 MB together; a small workload
+    is written whole."""
+    import bench
+
+    n = 16 * 2048 * 2048
+    idx = bench.dump_index(n, 8)
+    assert idx is not None and np.array_equal(idx, bench.dump_index(n, 8))
+    assert idx[0] >= 0 and idx[-1] < n and np.all(np.diff(idx) > 0)
+    np.save(tmp_path / "disparity_sample_index.npy", idx.astype(np.float64))
+    for t in range(8):
+        for kind in ("disparity", "fov_mask"):
+            np.save(tmp_path / ("%s_frame%d.npy" % (kind, t)), np.zeros(len(idx), np.float32))
+    assert 0.9 * bench.DUMP_BYTES < sum(f.stat().st_size for f in tmp_path.iterdir()) <= bench.DUMP_BYTES == 64 * 10**6
+    assert bench.dump_index(6 * 160 * 160, 4) is None

@@ -2,7 +2,7 @@
 # BASELINE config 4 (24 x 4096^2, single frame, destinations batched under the table budget): bench line +
 # HBM traffic passes -> gpurun_out/<tag>_* (tools/make_profiles.py <tag> cfg4 trims them into profiles/)
 tag=${1:-r06cfg4}
-ARGS="--config cfg4 --frames 1 --temporal 0 --no-cpu-baseline --no-single-frame"
+ARGS="--full --config cfg4 --frames 1 --temporal 0 --no-cpu-baseline --no-single-frame"
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 python bench.py --steps 2 --warmup 1 $ARGS > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err

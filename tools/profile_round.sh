@@ -7,6 +7,7 @@
 # PMC passes run `bench.py --steps 1 --warmup 0` (every kernel of the sequence once per frame); counters
 # never share a run with a trace domain.          usage: tools/profile_round.sh <tag> [bench args]
 tag=${1:-r03}; shift
+set -- --full "$@"  # every pass as bench.py --full: per-stage spans, roofline and result_crc in the line
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 python bench.py --steps 3 --warmup 1 "$@" > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err

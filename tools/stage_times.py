@@ -2,7 +2,7 @@
 """Developer tool: per-stage ms of one bench step (bench.py JSON on stdin or run inline)."""
 import json, subprocess, sys, os
 env = dict(os.environ)
-out = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + sys.argv[1:],
+out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + sys.argv[1:],
                      capture_output=True, text=True, env=env)
 try:
     d = json.loads(out.stdout.strip().splitlines()[-1])
