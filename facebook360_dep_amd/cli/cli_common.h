@@ -960,7 +960,9 @@ inline bool image_size(const fs::path& path, int& w, int& h) {
 // (blocks of 16 scan lines; OpenEXR's default, which OpenCV does not override), increasing-Y line order. Written
 // from the published file layout (openexr.com "OpenEXR File Layout"): magic, version, attribute list, line-offset
 // table, chunks; ZIP = byte de-interleave + delta predictor + zlib deflate, raw when deflate does not shrink it.
-inline void write_exr_f32(const fs::path& path, const float* m, int w, int h) {
+// channels = 3: m is interleaved B, G, R (cv::imwrite of a CV_32FC3 image): channels "B", "G", "R", each scan line
+// holding the channels one after the other in that (alphabetical) order.
+inline void write_exr_f32(const fs::path& path, const float* m, int w, int h, int channels = 1) {
   std::string hdr;
   auto put = [&](const void* p, size_t n) { hdr.append(static_cast<const char*>(p), n); };
   auto put_i32 = [&](int32_t v) { put(&v, 4); };
@@ -973,16 +975,20 @@ inline void write_exr_f32(const fs::path& path, const float* m, int w, int h) {
   };
   const unsigned char magic[8] = {0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0};  // magic, version 2, no flags
   put(magic, 8);
+  CHECK_MSG(channels == 1 || channels == 3, "write_exr_f32: 1 or 3 channels");
   {
-    std::string ch("Y");
-    ch.push_back('\0');
-    const int32_t pixelType = 2;  // FLOAT
-    ch.append(reinterpret_cast<const char*>(&pixelType), 4);
-    ch.append(std::string("\0\0\0\0", 4));  // pLinear + 3 reserved bytes
-    const int32_t one = 1;
-    ch.append(reinterpret_cast<const char*>(&one), 4);  // xSampling
-    ch.append(reinterpret_cast<const char*>(&one), 4);  // ySampling
-    ch.push_back('\0');                                 // end of the channel list
+    std::string ch;
+    for (int k = 0; k < channels; ++k) {
+      ch.append(channels == 1 ? "Y" : k == 0 ? "B" : k == 1 ? "G" : "R");
+      ch.push_back('\0');
+      const int32_t pixelType = 2;  // FLOAT
+      ch.append(reinterpret_cast<const char*>(&pixelType), 4);
+      ch.append(std::string("\0\0\0\0", 4));  // pLinear + 3 reserved bytes
+      const int32_t one = 1;
+      ch.append(reinterpret_cast<const char*>(&one), 4);  // xSampling
+      ch.append(reinterpret_cast<const char*>(&one), 4);  // ySampling
+    }
+    ch.push_back('\0');  // end of the channel list
     attr("channels", "chlist", ch);
   }
   attr("compression", "compression", std::string(1, (char)3));  // ZIP_COMPRESSION
@@ -1004,8 +1010,20 @@ inline void write_exr_f32(const fs::path& path, const float* m, int w, int h) {
   std::vector<unsigned char> tmp, packed;
   for (int b = 0; b < blocks; ++b) {
     const int y0 = b * kLines, lines = std::min(kLines, h - y0);
-    const size_t raw = (size_t)lines * w * 4;
+    const size_t raw = (size_t)lines * w * 4 * channels;
     const unsigned char* src = reinterpret_cast<const unsigned char*>(m + (size_t)y0 * w);
+    std::vector<float> planar;
+    if (channels > 1) {  // per scan line: all of B, then G, then R
+      planar.resize((size_t)lines * w * channels);
+      for (int l = 0; l < lines; ++l) {
+        for (int k = 0; k < channels; ++k) {
+          for (int x = 0; x < w; ++x) {
+            planar[((size_t)l * channels + k) * w + x] = m[(((size_t)(y0 + l)) * w + x) * channels + k];
+          }
+        }
+      }
+      src = reinterpret_cast<const unsigned char*>(planar.data());
+    }
     tmp.resize(raw);
     {  // even bytes first, odd bytes second; then each byte becomes its difference from the one before
       unsigned char *t1 = tmp.data(), *t2 = tmp.data() + (raw + 1) / 2;

@@ -46,6 +46,47 @@ class Options(C.Structure):
     ]
 
 
+class RenderParams(C.Structure):
+    """derp_render_params (include/derp_hip.h): one SimpleMeshRenderer view."""
+    _fields_ = [
+        ("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("position", C.c_double * 3),
+        ("forward", C.c_double * 3), ("up", C.c_double * 3), ("horizontal_fov", C.c_double), ("ipd", C.c_float),
+        ("alpha_blend", C.c_int32), ("disparity_color", C.c_int32), ("weight", C.c_int32), ("zero_nans", C.c_int32),
+    ]
+
+
+RENDER_KINDS = {"cube": 0, "equirect": 1, "snapshot": 2}
+WEIGHTS = {"svd": 0, "minor": 1}
+FORMATS = ["cubecolor", "cubedisp", "eqrcolor", "eqrdisp", "lr180", "snapcolor", "snapdisp", "tb3dof", "tbstereo"]
+
+
+def render_params(kind="equirect", width=3072, height=None, position=(0, 0, 0), forward=(-1, 0, 0), up=(0, 0, 1),
+                  horizontal_fov=90.0, ipd=0.0, alpha_blend=True, disparity_color=False, weight="svd", zero_nans=False):
+    """derp_render_params with SimpleMeshRenderer's defaults (height = width / 2)."""
+    p = RenderParams()
+    lib().derp_render_params_default(C.byref(p))
+    p.kind = RENDER_KINDS[kind]
+    p.width = width
+    p.height = width // 2 if height is None else height
+    for k, v in (("position", position), ("forward", forward), ("up", up)):
+        for i in range(3):
+            getattr(p, k)[i] = float(v[i])
+    p.horizontal_fov = horizontal_fov
+    p.ipd = ipd
+    p.alpha_blend = int(bool(alpha_blend))
+    p.disparity_color = int(bool(disparity_color))
+    p.weight = WEIGHTS[weight]
+    p.zero_nans = int(bool(zero_nans))
+    return p
+
+
+def render_format_size(fmt, width, height):
+    w, h = C.c_int(), C.c_int()
+    if lib().derp_render_format_size(fmt.encode(), width, height, C.byref(w), C.byref(h)):
+        raise ValueError("Invalid format: %s" % fmt)
+    return w.value, h.value
+
+
 # every symbol include/derp_hip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "derp_options_default", "derp_create", "derp_destroy", "derp_last_error", "derp_set_options", "derp_set_pyramid",
@@ -59,6 +100,8 @@ EXPORTS = [
     "derp_level_end", "derp_set_level_disparity", "derp_get_level_disparity", "derp_cost_map", "derp_debug_download",
     "derp_debug_atan2_ypos",
     "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
+    "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
+    "derp_render_vertices",
     "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
     "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
     "derp_get_counters", "derp_reset_counters", "derp_profile_enable", "derp_profile_reset", "derp_profile_query", "derp_profile_memoised",
@@ -405,6 +448,49 @@ class Derp:
         ctr = np.ascontiguousarray(centre, dtype=np.float64)
         out = np.zeros((6 * edge, edge, 4), dtype=np.float32)
         self._ck(lib().derp_canopy_cubemap(self.h, _p(inc), _p(ctr), edge, _p(out)))
+        return out
+
+    def render_upload(self, disps, colors=None):
+        """SimpleMeshRenderer's scene: disps[s] f32 [h, w], colors[s] float BGRA [h', w', 4] (own sizes) or None."""
+        disps = [np.ascontiguousarray(d, dtype=np.float32) for d in disps]
+        dp = (C.c_void_p * len(disps))(*[d.ctypes.data for d in disps])
+        dw = (C.c_int * len(disps))(*[d.shape[1] for d in disps])
+        dh = (C.c_int * len(disps))(*[d.shape[0] for d in disps])
+        if colors is None:
+            self._ck(lib().derp_render_upload(self.h, None, None, None, dp, dw, dh))
+            return
+        colors = [np.ascontiguousarray(c, dtype=np.float32) for c in colors]
+        assert all(c.ndim == 3 and c.shape[2] == 4 for c in colors)
+        cp = (C.c_void_p * len(colors))(*[c.ctypes.data for c in colors])
+        cw = (C.c_int * len(colors))(*[c.shape[1] for c in colors])
+        ch = (C.c_int * len(colors))(*[c.shape[0] for c in colors])
+        self._ck(lib().derp_render_upload(self.h, cp, cw, ch, dp, dw, dh))
+
+    def render(self, params, include=None):
+        """derp_render of the uploaded scene -> BGRA f32: cube [6 h, h, 4], equirect [h, 2 h, 4], snapshot [h, w, 4]."""
+        h = params.height
+        w = {0: h, 1: 2 * h, 2: params.width}[params.kind]
+        out = np.zeros((6 * h if params.kind == 0 else h, w, 4), dtype=np.float32)
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.uint8)
+        self._ck(lib().derp_render(self.h, C.byref(params), None if inc is None else _p(inc), _p(out)))
+        return out
+
+    def render_format(self, fmt, params, background=None, background_equirect=None):
+        """One SimpleMeshRenderer --format, stacked and composited -> BGRA f32."""
+        w, h = render_format_size(fmt, params.width, params.height)
+        out = np.zeros((h, w, 4), dtype=np.float32)
+        bg = None if background is None else np.ascontiguousarray(background, dtype=np.float32)
+        eq = None if background_equirect is None else np.ascontiguousarray(background_equirect, dtype=np.float32)
+        assert bg is None or bg.shape == out.shape
+        self._ck(lib().derp_render_format(self.h, fmt.encode(), C.byref(params), None if bg is None else _p(bg),
+                                          None if eq is None else _p(eq), 0 if eq is None else eq.shape[1],
+                                          0 if eq is None else eq.shape[0], _p(out)))
+        return out
+
+    def render_vertices(self, cam, shape, ipd):
+        """camera `cam`'s mesh vertices after canopyVS's stereo stage (ipd 0: none) -> f32 [h, w, 4]."""
+        out = np.zeros((shape[0], shape[1], 4), dtype=np.float32)
+        self._ck(lib().derp_render_vertices(self.h, cam, C.c_float(ipd), _p(out)))
         return out
 
     def fov_mask(self, d, w, h):

@@ -36,8 +36,9 @@ def read_pfm(path):
 
 
 def read_exr(path):
-    """Single-part scan-line OpenEXR with one FLOAT channel (what cv::imwrite writes for a CV_32FC1 disparity and
-    what this build's executables write for --output_formats=exr): NO / ZIPS / ZIP compression."""
+    """Single-part scan-line OpenEXR with FLOAT channels (what cv::imwrite writes for a CV_32FC1 disparity and
+    what this build's executables write for --output_formats=exr; SimpleMeshRenderer's B, G, R for --file_type=exr):
+    NO / ZIPS / ZIP compression. One channel -> [h, w]; several -> [h, w, C] in the file's (alphabetical) order."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:4] != b"\x76\x2f\x31\x01":
@@ -55,11 +56,16 @@ def read_exr(path):
         attrs[name] = (typ, data[e2 + 5:e2 + 5 + size])
         pos = e2 + 5 + size
     pos += 1
-    ch = attrs["channels"][1]
-    e = ch.index(b"\0")
-    ptype, = struct.unpack_from("<i", ch, e + 1)
-    if ch[e + 17:] != b"\0" or ptype != 2:
-        raise ValueError("expected exactly one FLOAT channel: %s" % path)
+    ch, cpos, nch = attrs["channels"][1], 0, 0
+    while ch[cpos] != 0:
+        e = ch.index(b"\0", cpos)
+        ptype, = struct.unpack_from("<i", ch, e + 1)
+        if ptype != 2:
+            raise ValueError("expected FLOAT channels: %s" % path)
+        nch += 1
+        cpos = e + 17
+    if nch < 1 or ch[cpos:] != b"\0":
+        raise ValueError("bad channel list: %s" % path)
     comp = attrs["compression"][1][0]
     x0, y0, x1, y1 = struct.unpack("<4i", attrs["dataWindow"][1])
     w, h = x1 - x0 + 1, y1 - y0 + 1
@@ -68,11 +74,11 @@ def read_exr(path):
         raise ValueError("unsupported compression %d: %s" % (comp, path))
     blocks = (h + lines - 1) // lines
     offsets = struct.unpack_from("<%dQ" % blocks, data, pos)
-    out = np.empty((h, w), dtype=np.float32)
+    out = np.empty((h, nch, w), dtype=np.float32)
     for off in offsets:
         y, size = struct.unpack_from("<ii", data, off)
         n = min(lines, y1 - y + 1)
-        raw = n * w * 4
+        raw = n * w * 4 * nch
         buf = data[off + 8:off + 8 + size]
         if comp != 0 and size < raw:
             t = np.frombuffer(zlib.decompress(buf), dtype=np.uint8).astype(np.int64)
@@ -81,8 +87,8 @@ def read_exr(path):
             px = np.empty(raw, dtype=np.uint8)
             px[0::2], px[1::2] = t[:half], t[half:]
             buf = px.tobytes()
-        out[y - y0:y - y0 + n] = np.frombuffer(buf, dtype="<f4", count=n * w).reshape(n, w)
-    return out
+        out[y - y0:y - y0 + n] = np.frombuffer(buf, dtype="<f4", count=n * w * nch).reshape(n, nch, w)
+    return out[:, 0, :].copy() if nch == 1 else np.ascontiguousarray(out.transpose(0, 2, 1))
 
 
 def _chunk(tag, payload):

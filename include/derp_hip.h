@@ -226,6 +226,42 @@ int derp_rephotograph_render(derp_ctx* ctx, int target, float* out_bgra);
  * top to bottom: out = BGRA float [6 * edge][edge][4], alpha in {0, 1}. generateCubemaps(removeOne(i)) =
  * include everything but i; the reference side = include only i (ComputeRephotographyErrors.cpp:140-145). */
 int derp_canopy_cubemap(derp_ctx* ctx, const uint8_t* include, const double* centre, int edge, float* out_bgra);
+/* SimpleMeshRenderer's renderer without OpenGL (source/render/SimpleMeshRenderer.cpp, CanopyScene.cpp:15-69, 72-266,
+ * 288-475, DisparityColor.h:18-57): the engine of derp_canopy_cubemap for any view. Conventions of this group:
+ * colour textures float BGRA [h][w][4] (a loaded cv::Vec4f image; stored as GL_RGBA16), disparities f32, every
+ * camera with its own texture and disparity size; outputs BGRA float with NaN where nothing was rendered.
+ * derp_render_upload: the scene (CanopyScene::CanopyScene). colors may be NULL (no colour; disparity formats only).
+ * derp_render: one image of the cameras include[s] != 0 (include NULL = all) per derp_render_params:
+ *   CUBE      CanopyScene::cubemap(height): six height x height faces stacked, out [6 h][h][4];
+ *   EQUIRECT  CanopyScene::equirect(height): out [h][2 h][4], row 0 = north;
+ *   SNAPSHOT  the snapshot of SimpleMeshRenderer.cpp:386-405 (frustum of horizontal_fov, posForwardUp): [h][w][4].
+ * derp_render_format: a whole SimpleMeshRenderer --format (cubecolor cubedisp eqrcolor eqrdisp lr180 snapcolor
+ *   snapdisp tb3dof tbstereo) with its stacks and generate() compositing (--background: background [out_h][out_w][4]
+ *   or NULL; --background_equirect: [eq_h][eq_w][4] or NULL); derp_render_format_size gives out_w x out_h.
+ * derp_render_vertices: camera `cam`'s mesh vertices after canopyVS's stereo stage for half-IPD `ipd` (0 = none),
+ *   xyz + 0 [dh][dw][4] (the test hook for the device's transcendental functions). */
+enum { DERP_RENDER_CUBE = 0, DERP_RENDER_EQUIRECT = 1, DERP_RENDER_SNAPSHOT = 2 };
+enum { DERP_WEIGHT_SVD = 0, DERP_WEIGHT_MINOR = 1 };
+typedef struct {
+  int32_t kind;            /* DERP_RENDER_* */
+  int32_t width, height;   /* snapshot viewport; cube edge and equirect height = height */
+  double position[3];      /* --position (rig space) */
+  double forward[3], up[3];/* --forward, --up (snapshot and the background equirect's ray) */
+  double horizontal_fov;   /* --horizontal_fov, degrees */
+  float ipd;               /* canopyVS ipdm: +0.032 left eye, -0.032 right eye, 0 mono */
+  int32_t alpha_blend;     /* accumulateFS alphaBlend (!--ignore_alpha_blend) */
+  int32_t disparity_color; /* 0: the colour textures, 1: the disparity colours seen from position */
+  int32_t weight;          /* DERP_WEIGHT_SVD (SimpleMeshRenderer) or DERP_WEIGHT_MINOR (rephotography) */
+  int32_t zero_nans;       /* ComputeRephotographyErrors' zeroOutNans after un-premultiplying */
+} derp_render_params;
+void derp_render_params_default(derp_render_params* p);
+int derp_render_upload(derp_ctx* ctx, const float* const* colors_bgra, const int* color_w, const int* color_h,
+                       const float* const* disparities, const int* disp_w, const int* disp_h);
+int derp_render(derp_ctx* ctx, const derp_render_params* p, const uint8_t* include, float* out_bgra);
+int derp_render_format_size(const char* format, int width, int height, int* out_w, int* out_h);
+int derp_render_format(derp_ctx* ctx, const char* format, const derp_render_params* p, const float* background,
+                       const float* background_equirect, int eq_w, int eq_h, float* out_bgra);
+int derp_render_vertices(derp_ctx* ctx, int cam, float ipd, float* out_xyzw);
 /* generateFovMasks for one destination camera at an arbitrary size (DerpUtil.cpp:259-276) */
 int derp_fov_mask(derp_ctx* ctx, int dst, int w, int h, uint8_t* out);
 /* upsampleDisparities for one camera (UpsampleDisparityLib.cpp:98-182). fg_mask / fg_mask_up /
