@@ -163,6 +163,9 @@ struct derp_ctx {
 
   bool profiling = false;
   bool noMemo = false;  // DERP_NO_MEMO (developer switch), read once in derp_create
+  // ping-pong's candidate loop: compacted into full waves of (pixel, candidate) tasks, or one pixel per lane
+  // (DERP_PP_COMPACT=0, developer A/B switch; same results), read once in derp_create
+  bool ppCompact = true;
   // waves per SIMD of the random-proposal / ping-pong kernels (0 = what their registers and LDS allow: four up to 16
   // cameras): a launch can ask for fewer by reserving more LDS per (one-wave) block — DERP_RANDOM_WAVES / DERP_PP_WAVES,
   // developer A/B switches
@@ -708,8 +711,10 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->ppWaves, c->ldsPerCu, kCostLdsStatic);
+  const bool four = cost_four_waves(c);
+  const auto kernel = c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3);
   for (int it = 1; it <= c->opt.ping_pong_iterations; ++it) {
-    hipLaunchKernelGGL(cost_four_waves(c) ? k_ping_pong : k_ping_pong_w3, dim3(round8(tiles), nd), dim3(DERP_COST_BLOCK), lds,
+    hipLaunchKernelGGL(kernel, dim3(round8(tiles), nd), dim3(DERP_COST_BLOCK), lds,
                        c->stream, V, c->changed.as<uint8_t>(), c->dispRes.as<float>(), c->costRes.as<float>(), tilesX,
                        (int)(it == 1 && c->randomRanThisLevel && !c->noMemo));
     KCHECK(c);
@@ -1516,6 +1521,9 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
     c->xcdRotate = atoi(e);
   }
   c->noMemo = getenv("DERP_NO_MEMO") != nullptr;
+  if (const char* e = getenv("DERP_PP_COMPACT")) {
+    c->ppCompact = atoi(e) != 0;
+  }
   if (const char* e = getenv("DERP_RANDOM_WAVES")) {
     c->randomWaves = atoi(e);
   }

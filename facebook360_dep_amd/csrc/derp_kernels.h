@@ -983,8 +983,11 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
 }
 
 // gather the per-pixel constants of computeCost: dst ray, 3x3 dst patch, dst bias, variance
+// `tl`: the pixel's place in the wave's 8x8 tile (y * 8 + x, tile-local), which picks its corner of the window — the lane's
+// own pixel unless a compacted ping-pong task evaluates another lane's
 template <bool WITH_RAY = true>
-__device__ __forceinline__ void load_pixctx(const LevelView& V, int d, int own, int x, int y, const PatchWin* win, PixCtx& px) {
+__device__ __forceinline__ void load_pixctx(const LevelView& V, int d, int own, int x, int y, const PatchWin* win, PixCtx& px,
+                                            int tl = -1) {
   const Cam& cd = V.camsDst[d];
   px.rayO = {cd.pos[0], cd.pos[1], cd.pos[2]};
   // the ray direction of the pixel centre (Camera::rig of p = ((x + .5) / W, (y + .5) / H): undistort's Newton
@@ -997,7 +1000,10 @@ __device__ __forceinline__ void load_pixctx(const LevelView& V, int d, int own, 
     px.rayD = {V.rayDir[i], V.rayDir[V.rayStride + i], V.rayDir[2 * V.rayStride + i]};
   }
   // the 3x3 patch: the lane's corner of the wave's window (patch_window_fill)
-  const int corner = (int)((threadIdx.x & 63) >> 3) * kWinW + (int)(threadIdx.x & 7);
+  if (tl < 0) {
+    tl = (int)(threadIdx.x & 63);
+  }
+  const int corner = (tl >> 3) * kWinW + (tl & 7);
   px.winBG = win->bg + corner;
   px.winR = win->r + corner;
   const ushort4 b = V.ownBias[(size_t)own * n + (size_t)y * V.W + x];
@@ -1775,7 +1781,244 @@ __global__ void __launch_bounds__(DERP_COST_BLOCK, 3)
 // ping-pong propagation — Derp.cpp:403-538. Jacobi: reads disparity, writes dispRes / costRes.
 // ----------------------------------------------------------------------------------------
 __constant__ int kCandidates[9][2] = {{0, 0}, {-1, 0}, {1, 0}, {0, -1}, {0, 1}, {-2, -2}, {2, -2}, {-2, 2}, {2, 2}};
+// the same offsets as immediates for the compacted loop, where k differs per lane: (offset + 2) in 3 bits per candidate
+constexpr int kCandOff[9][2] = {{0, 0}, {-1, 0}, {1, 0}, {0, -1}, {0, 1}, {-2, -2}, {2, -2}, {-2, 2}, {2, 2}};
+constexpr unsigned cand_pack(int c) {
+  unsigned p = 0;
+  for (int k = 0; k < 9; ++k) {
+    p |= (unsigned)(kCandOff[k][c] + 2) << (3 * k);
+  }
+  return p;
+}
+constexpr unsigned kCandPackX = cand_pack(0), kCandPackY = cand_pack(1);
 
+// Developer measurement (-DDERP_COUNT_PP_FILL): ping-pong's counter slot [1] holds the lane-slots its waves walk through
+// computeCost (64 per wave entry) INSTEAD of the pair count; evaluations / lane-slots = the fill of the candidate loop
+// (tools/pp_fill_probe.py).
+#ifdef DERP_COUNT_PP_FILL
+__device__ __forceinline__ unsigned pp_fill_entry() {
+  return __builtin_ctzll(__ballot(1)) == (int)(threadIdx.x & 63) ? 64u : 0u;
+}
+#endif
+
+// Candidate loop of one pixel per lane (DERP_PP_COMPACT=0): the wave enters computeCost for candidate k when ANY lane
+// needs it, the others ride along masked off.
+__device__ __forceinline__ void ping_pong_candidates_loop(const LevelView& V, const uint8_t* __restrict__ changed, int dl, int x,
+                                                          int y, const PatchWin* win, LdsPairs& pairs, int useMemo, float& outDisp,
+                                                          float& outCost, unsigned& counts, unsigned& fillSlots, PhaseTimers& tm) {
+  const int d = V.dst0 + dl;
+  const int own = V.dst2src[d];
+  // per-destination planes (wave-uniform bases) and a 32-bit pixel index: the loads take the scalar-base + 32-bit
+  // offset form, and nothing 64-bit per lane has to survive the candidate loop
+  const size_t n = (size_t)V.W * V.H;
+  const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
+  const float* disp = V.disparity + (size_t)d * n;
+  const uint8_t* fov = V.fovMask + (size_t)d * n;
+  const uint8_t* chg = changed + (size_t)d * n;
+  outDisp = disp[idx];
+  const bool interior = x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1;
+  if (interior && fov[idx]) {
+    if (!V.srcFg[(size_t)own * n + idx]) {
+      outDisp = V.bgDisp[(size_t)d * n + idx];
+    } else if (!(V.srcVar[(size_t)own * n + idx] < V.varNoiseFloor)) {
+      PixCtx px;
+      load_pixctx<!DERP_PP_RELOAD_RAY>(V, d, own, x, y, win, px);
+      const unsigned cull = DERP_SOURCE_CULL ? behind_sources(V, d, idx) : 0u;
+      float bestCost = __builtin_inff();
+      float bestDisp = outDisp;
+      // what the candidate loop carries per lane: the pixel (x | y << 16), the best candidate so far, the counters.
+      // Everything else is derived again per candidate from an opaque copy of `xy` (four plain instructions) instead
+      // of riding through computeCost's registers: x, y, the pixel index, the background disparity.
+      const unsigned xy = (unsigned)x | ((unsigned)y << 16);
+      for (int k = 0; k < 9; ++k) {
+        unsigned q = xy;
+        asm("" : "+v"(q) : "s"(k));
+        const int px0 = (int)(q & 0xffffu), py0 = (int)(q >> 16);
+        const unsigned pidx = (unsigned)py0 * (unsigned)V.W + (unsigned)px0;
+        const int xx = min(max(px0 + kCandidates[k][0], 0), V.W - 1);
+        const int yy = min(max(py0 + kCandidates[k][1], 0), V.H - 1);
+        const unsigned j = (unsigned)yy * (unsigned)V.W + (unsigned)xx;
+        if (fov[j]) {
+          const float cand = disp[j];
+          const float bg = V.hasFg ? (V.bgDisp + (size_t)d * n)[pidx] : 0.f;
+          if (cand >= bg && chg[j]) {
+            float2 r;
+            // Candidate (0,0) is the pixel's own disparity. In the first iteration, where random
+            // proposals evaluated this pixel, computeCost(own disparity) is exactly the value they
+            // left in cost / confidence (a pure function of the same arguments): reuse it.
+            const float memoConf = (k == 0 && useMemo) ? (V.confidence + (size_t)d * n)[pidx] : 0.0f;
+            if (memoConf != 0.0f) {
+              r = make_float2((V.cost + (size_t)d * n)[pidx], memoConf);
+              counts += (unsigned)(V.pairCount + (size_t)d * n)[pidx] + (1u << 24);
+            } else {
+              unsigned np = 0;
+#ifdef DERP_COUNT_PP_FILL
+              fillSlots += pp_fill_entry();
+#endif
+              r = compute_cost<DERP_COST_SSD_SCALAR != 0, false, DERP_PP_RELOAD_RAY != 0>(V, dl, own, px, cand, pairs, np, cull, pidx, nullptr, &tm);
+              counts += np;
+            }
+            counts += 1u << 16;
+            if (r.x < bestCost) {
+              bestCost = r.x;
+              bestDisp = cand;
+            }
+          }
+        }
+      }
+      outDisp = bestDisp;
+      outCost = bestCost;
+    }
+  }
+}
+
+// Compacted candidate loop (DERP_PP_COMPACT=1, the default). The wave still owns its 8x8 tile, window and cull mask, but
+// runs computeCost over full batches of (pixel, candidate) tasks instead of one candidate index for all 64 pixels:
+//  1. owner pass: every lane builds its pixel's 9-bit candidate mask with the loop's predicates in the loop's order; a
+//     memoised candidate 0 is folded in right there (it is first in the order) and stays out of the mask;
+//  2. a wave prefix sum over the masks' popcounts lays the tasks out as one list, each pixel's tasks contiguous and in
+//     ascending k;
+//  3. task t = base + lane finds its owner pixel (binary search over the prefixes) and k (the (t - start)-th set bit of
+//     the owner's mask), rebuilds the owner's context and runs computeCost;
+//  4. every task lane stages (cost, candidate) in its spare pair slot (slot S - 1, which ping-pong never uses); the owners
+//     walk their staged entries in list order with the loop's strict `<`: the same comparisons in the same order, so
+//     ties and NaNs resolve as before.
+// The cull mask is taken over the tile's evaluating pixels, as in the loop: it holds for any subset of them.
+__device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V, const uint8_t* __restrict__ changed, int dl, int& x,
+                                                             int& y, const PatchWin* win, LdsPairs& pairs, int useMemo, float& outDisp,
+                                                             float& outCost, unsigned& counts, unsigned& fillSlots, PhaseTimers& tm) {
+  const int d = V.dst0 + dl;
+  const int own = V.dst2src[d];
+  const size_t n = (size_t)V.W * V.H;
+  const int lane = (int)(threadIdx.x & 63);
+  const float* disp = V.disparity + (size_t)d * n;
+  const uint8_t* fov = V.fovMask + (size_t)d * n;
+  const uint8_t* chg = changed + (size_t)d * n;
+  // 1. owner pass
+  unsigned cmask = 0;
+  bool eval = false;
+  const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
+  if (x < V.W && y < V.H) {
+    outDisp = disp[idx];
+    const bool interior = x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1;
+    if (interior && fov[idx]) {
+      if (!V.srcFg[(size_t)own * n + idx]) {
+        outDisp = V.bgDisp[(size_t)d * n + idx];
+      } else if (!(V.srcVar[(size_t)own * n + idx] < V.varNoiseFloor)) {
+        eval = true;
+        const float bg = V.hasFg ? (V.bgDisp + (size_t)d * n)[idx] : 0.f;
+        for (int k = 0; k < 9; ++k) {
+          const int xx = min(max(x + (int)((kCandPackX >> (3 * k)) & 7u) - 2, 0), V.W - 1);
+          const int yy = min(max(y + (int)((kCandPackY >> (3 * k)) & 7u) - 2, 0), V.H - 1);
+          const unsigned j = (unsigned)yy * (unsigned)V.W + (unsigned)xx;
+          if (fov[j]) {
+            const float cand = disp[j];
+            if (cand >= bg && chg[j]) {
+              const float memoConf = (k == 0 && useMemo) ? (V.confidence + (size_t)d * n)[idx] : 0.0f;
+              if (memoConf != 0.0f) {
+                const float c = (V.cost + (size_t)d * n)[idx];
+                counts += (unsigned)(V.pairCount + (size_t)d * n)[idx] + (1u << 24) + (1u << 16);
+                if (c < outCost) {
+                  outCost = c;
+                  outDisp = cand;
+                }
+              } else {
+                cmask |= 1u << k;
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+  // the cull mask of the evaluating lanes (behind_sources' ballot, with the other lanes made neutral)
+  unsigned cull = 0;
+  if (DERP_SOURCE_CULL) {
+    const unsigned m = eval ? V.behind[(size_t)d * n + idx] : ~0u;
+    for (int t = 0; t < V.S - 1; ++t) {
+      if (__ballot(!((m >> t) & 1u)) == 0ull) {
+        cull |= 1u << t;
+      }
+    }
+    cull = __builtin_amdgcn_readfirstlane(cull);
+  }
+  // 2. the task list: inclusive prefix sum of the per-pixel task counts
+  int incl = __popc(cmask);
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __builtin_amdgcn_ds_bpermute((lane - off) << 2, incl);
+    if (lane >= off) {
+      incl += v;
+    }
+  }
+  const int total = __builtin_amdgcn_readlane(incl, 63);
+  // What the batches carry per lane: the pixel's best candidate, the counters, and its mask and the end of its tasks in
+  // the list, packed in one register (the start is the end minus the mask's popcount). Everything else — the lane, the
+  // pair slots, the pixel itself — is derived again per batch from an opaque copy of the lane index and wave-uniform
+  // values, instead of riding through computeCost's registers (where the allocator spilled them).
+  const unsigned list = cmask | ((unsigned)incl << 16);
+  const int x0 = __builtin_amdgcn_readfirstlane(x - (lane & 7)), y0 = __builtin_amdgcn_readfirstlane(y - (lane >> 3));
+  extern __shared__ SsdPair ldsPairs[];
+  SsdPair* const wavePairs = ldsPairs + (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63u);
+  SsdPair* const stage = wavePairs + (size_t)(V.S - 1) * pairs.stride;  // the spare pair slot of every lane of the wave
+  // 3. full batches
+  for (int base = 0; base < total; base += 64) {
+    int ln = lane;
+    asm("" : "+v"(ln) : "s"(base));
+    const int t = base + ln;
+    // owner = the number of pixels whose tasks all lie before t
+    int o = 0;
+    for (int step = 32; step > 0; step >>= 1) {
+      if ((int)((unsigned)__builtin_amdgcn_ds_bpermute((o + step - 1) << 2, (int)list) >> 16) <= t) {
+        o += step;
+      }
+    }
+    o = min(o, 63);
+    const unsigned ol = (unsigned)__builtin_amdgcn_ds_bpermute(o << 2, (int)list);
+    unsigned m = ol & 0xffffu;
+    const int oStart = (int)(ol >> 16) - __popc(m);
+#ifdef DERP_COUNT_PP_FILL
+    fillSlots += ln == 0 ? 64u : 0u;
+#endif
+    if (t < total) {
+      for (int r = t - oStart; r > 0; --r) {
+        m &= m - 1;
+      }
+      const int k = __builtin_ctz(m);
+      const int ox = x0 + (o & 7), oy = y0 + (o >> 3);
+      const unsigned pidx = (unsigned)oy * (unsigned)V.W + (unsigned)ox;
+      const int xx = min(max(ox + (int)((kCandPackX >> (3 * k)) & 7u) - 2, 0), V.W - 1);
+      const int yy = min(max(oy + (int)((kCandPackY >> (3 * k)) & 7u) - 2, 0), V.H - 1);
+      const float cand = disp[(unsigned)yy * (unsigned)V.W + (unsigned)xx];
+      PixCtx px;
+      load_pixctx<!DERP_PP_RELOAD_RAY>(V, d, own, ox, oy, win, px, o);
+      LdsPairs lp{wavePairs + ln, pairs.stride, pairs.atanLut};
+      unsigned np = 0;
+      const float2 r = compute_cost<DERP_COST_SSD_SCALAR != 0, false, DERP_PP_RELOAD_RAY != 0>(V, dl, own, px, cand, lp, np, cull, pidx, nullptr, &tm);
+      counts += np + (1u << 16);
+      int sl = lane;
+      asm("" : "+v"(sl) : "v"(r.x));
+      stage[sl] = SsdPair{r.x, cand};
+    }
+    // 4. fold: one wave reads what its own lanes wrote (LDS serves a wave in order; the fence keeps the compiler's order)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int end = (int)(list >> 16);
+    const int lo = max(end - __popc(list & 0xffffu), base), hi = min(end, base + 64);
+    for (int i = lo; i < hi; ++i) {
+      const SsdPair e = stage[i - base];
+      if (e.first < outCost) {
+        outCost = e.first;
+        outDisp = e.second;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  x = x0 + (lane & 7);
+  y = y0 + (lane >> 3);
+}
+
+template <bool COMPACT>
 __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                                                float* __restrict__ costRes, int tilesX, int useMemo) {
   extern __shared__ SsdPair ldsPairs[];
@@ -1795,76 +2038,23 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
   LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
 #endif
   __syncthreads();
-  // per-lane counters in one register: pairs (bits 0..15: <= 9 * 31), cost evaluations (16..23: <= 9), memoised (24..)
-  unsigned counts = 0;
+  // per-lane counters in one register: pairs (bits 0..15: <= 10 * 31), cost evaluations (16..23: <= 10), memoised (24..)
+  unsigned counts = 0, fillSlots = 0;
   PhaseTimers tm;
   const unsigned tk0 = phase_clock();
+  float outDisp = 0.f;
+  float outCost = __builtin_inff();
+  if constexpr (COMPACT) {
+    // (every lane takes part: the task list is built and walked with wave-wide shuffles)
+    ping_pong_candidates_compact(V, changed, dl, x, y, win, pairs, useMemo, outDisp, outCost, counts, fillSlots, tm);
+  } else if (x < V.W && y < V.H) {
+    ping_pong_candidates_loop(V, changed, dl, x, y, win, pairs, useMemo, outDisp, outCost, counts, fillSlots, tm);
+  }
   if (x < V.W && y < V.H) {
-    const int own = V.dst2src[d];
-    // per-destination planes (wave-uniform bases) and a 32-bit pixel index: the loads take the scalar-base + 32-bit
-    // offset form, and nothing 64-bit per lane has to survive the candidate loop
     const size_t n = (size_t)V.W * V.H;
     const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
-    const float* disp = V.disparity + (size_t)d * n;
-    const uint8_t* fov = V.fovMask + (size_t)d * n;
-    const uint8_t* chg = changed + (size_t)d * n;
-    dispRes += (size_t)d * n;
-    costRes += (size_t)d * n;
-    float outDisp = disp[idx];
-    float outCost = __builtin_inff();
-    const bool interior = x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1;
-    if (interior && fov[idx]) {
-      if (!V.srcFg[(size_t)own * n + idx]) {
-        outDisp = V.bgDisp[(size_t)d * n + idx];
-      } else if (!(V.srcVar[(size_t)own * n + idx] < V.varNoiseFloor)) {
-        PixCtx px;
-        load_pixctx<!DERP_PP_RELOAD_RAY>(V, d, own, x, y, win, px);
-        const unsigned cull = DERP_SOURCE_CULL ? behind_sources(V, d, idx) : 0u;
-        float bestCost = __builtin_inff();
-        float bestDisp = outDisp;
-        // what the candidate loop carries per lane: the pixel (x | y << 16), the best candidate so far, the counters.
-        // Everything else is derived again per candidate from an opaque copy of `xy` (four plain instructions) instead
-        // of riding through computeCost's registers: x, y, the pixel index, the background disparity.
-        const unsigned xy = (unsigned)x | ((unsigned)y << 16);
-        for (int k = 0; k < 9; ++k) {
-          unsigned q = xy;
-          asm("" : "+v"(q) : "s"(k));
-          const int px0 = (int)(q & 0xffffu), py0 = (int)(q >> 16);
-          const unsigned pidx = (unsigned)py0 * (unsigned)V.W + (unsigned)px0;
-          const int xx = min(max(px0 + kCandidates[k][0], 0), V.W - 1);
-          const int yy = min(max(py0 + kCandidates[k][1], 0), V.H - 1);
-          const unsigned j = (unsigned)yy * (unsigned)V.W + (unsigned)xx;
-          if (fov[j]) {
-            const float cand = disp[j];
-            const float bg = V.hasFg ? (V.bgDisp + (size_t)d * n)[pidx] : 0.f;
-            if (cand >= bg && chg[j]) {
-              float2 r;
-              // Candidate (0,0) is the pixel's own disparity. In the first iteration, where random
-              // proposals evaluated this pixel, computeCost(own disparity) is exactly the value they
-              // left in cost / confidence (a pure function of the same arguments): reuse it.
-              const float memoConf = (k == 0 && useMemo) ? (V.confidence + (size_t)d * n)[pidx] : 0.0f;
-              if (memoConf != 0.0f) {
-                r = make_float2((V.cost + (size_t)d * n)[pidx], memoConf);
-                counts += (unsigned)(V.pairCount + (size_t)d * n)[pidx] + (1u << 24);
-              } else {
-                unsigned np = 0;
-                r = compute_cost<DERP_COST_SSD_SCALAR != 0, false, DERP_PP_RELOAD_RAY != 0>(V, dl, own, px, cand, pairs, np, cull, pidx, nullptr, &tm);
-                counts += np;
-              }
-              counts += 1u << 16;
-              if (r.x < bestCost) {
-                bestCost = r.x;
-                bestDisp = cand;
-              }
-            }
-          }
-        }
-        outDisp = bestDisp;
-        outCost = bestCost;
-      }
-    }
-    dispRes[idx] = outDisp;
-    costRes[idx] = outCost;
+    (dispRes + (size_t)d * n)[idx] = outDisp;
+    (costRes + (size_t)d * n)[idx] = outCost;
   }
 #if DERP_PHASE_TIMERS
   if ((threadIdx.x & 63) == 0) {
@@ -1876,7 +2066,12 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
   return;
 #endif
   unsigned nMemo = counts >> 24;
+#ifdef DERP_COUNT_PP_FILL
+  flush_counters(V, (counts >> 16) & 0xffu, fillSlots);
+#else
+  (void)fillSlots;
   flush_counters(V, (counts >> 16) & 0xffu, counts & 0xffffu);
+#endif
   for (int off = 32; off > 0; off >>= 1) {
     nMemo += __shfl_down(nMemo, off);
   }
@@ -1885,15 +2080,27 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
   }
 }
 
+// Two register budgets (see k_random_proposals_w3) x two candidate loops: the compacted one, and the one-pixel-per-lane
+// loop it replaced (DERP_PP_COMPACT=0, developer A/B). The launcher picks (run_ping_pong, derp_capi.hip).
 __global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
     k_ping_pong(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                 float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body(V, changed, dispRes, costRes, tilesX, useMemo);
+  ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
 }
 __global__ void __launch_bounds__(DERP_COST_BLOCK, 3)  // more than 16 cameras: see k_random_proposals_w3
     k_ping_pong_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                    float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body(V, changed, dispRes, costRes, tilesX, useMemo);
+  ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
+}
+__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
+    k_ping_pong_loop(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
+                     float* __restrict__ costRes, int tilesX, int useMemo) {
+  ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
+}
+__global__ void __launch_bounds__(DERP_COST_BLOCK, 3)
+    k_ping_pong_loop_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
+                        float* __restrict__ costRes, int tilesX, int useMemo) {
+  ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
 }
 
 // changed = disp != dispRes; dispRes -> disp; costRes -> cost (Derp.cpp:527-529)
