@@ -78,9 +78,14 @@ DERP_HD double undistort(const Cam& c, const double y) {
 
 static constexpr int kAtanLutDoubles = 20;  // atan2_ypos_lut's table: 5 rows of {atanhi, atanlo, c, pad}
 #if defined(__HIP_DEVICE_COMPILE__)
-// IEEE fp64 division for operands whose quotient neither overflows nor underflows: the reciprocal-refinement
-// sequence the compiler emits for `/` (two Newton steps, quotient, one correction) without its exponent
-// pre-scaling and special-case fix-up — the same roundings, so the same correctly rounded quotient.
+// fp64 division: the reciprocal-refinement sequence the compiler emits for `/` (two Newton steps, quotient, one
+// correction) without its exponent pre-scaling (v_div_scale) and special-case fix-up (v_div_fixup). Where those two
+// do nothing it takes the same roundings, so it returns the correctly rounded quotient, bit for bit: for
+// 2^-968 <= |n| < 2^1023, 2^-1021 <= |d| < 2^1021 and 2^-1000 <= |n / d| < 2^766, and for n = +0
+// (tests/test_gpu_fp64_primitives.py). Outside that domain it is not IEEE: n = -0 gives +0; d = +-0 and
+// |d| < 2^-1024 give NaN (the reciprocal overflows to inf); divisors near 2^-1022 and numerators below 2^-968 can
+// lose the last bit to an underflowing residual. The projection's operands (xy, distort(r), atan2's reduction)
+// lie well inside the domain except at xy == 0, where the reference's quotient is 0 / 0 = NaN as well.
 __device__ __forceinline__ double div_plain(double n, double d) {
   double r = __builtin_amdgcn_rcp(d);
   r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);

@@ -2012,6 +2012,41 @@ int derp_debug_atan2_ypos(derp_ctx* c, const double* y, const double* x, double*
   return 0;
 }
 
+int derp_debug_fp64(derp_ctx* c, int op, const double* a, const double* b, double* out, size_t n) {
+  if (!c || !a || !out || op < 0 || op > 3 || (op >= 2 && !b)) {
+    return fail(c, "bad arguments");
+  }
+  if (n == 0) {
+    return 0;
+  }
+  ALLOC(c, c->staging, 3 * n * sizeof(double));
+  double* d = c->staging.as<double>();
+  HIPCHK(c, hipMemcpyAsync(d, a, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d + n, op >= 2 ? b : a, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_debug_fp64, dim3(flat_grid(n)), dim3(256), 0, c->stream, op, d, d + n, d + 2 * n, n);
+  KCHECK(c);
+  HIPCHK(c, hipMemcpyAsync(out, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int derp_debug_sees(derp_ctx* c, int src, const double* xyz, size_t n, double* out) {
+  if (!c || !xyz || !out || src < 0 || src >= c->S) {
+    return fail(c, "bad arguments");
+  }
+  if (n == 0) {
+    return 0;
+  }
+  ALLOC(c, c->staging, 9 * n * sizeof(double));
+  double* d = c->staging.as<double>();
+  HIPCHK(c, hipMemcpyAsync(d, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_debug_sees, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->camsSrc.as<Cam>(), src, d, d + 3 * n, n);
+  KCHECK(c);
+  HIPCHK(c, hipMemcpyAsync(out, d + 3 * n, 6 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
   TRY(need_current(c, false));
   const int L = c->cur;

@@ -826,6 +826,15 @@ __device__ __forceinline__ unsigned phase_clock() {
   return 0u;
 #endif
 }
+// The LEAN variant of `sees` (derp_camera.h) the cost kernels project through: ping-pong, brute force and the cost map
+// (RANDOM = false) and random proposals (RANDOM = true; bit 2: square roots through sqrt_lean, where its three registers
+// decide between scratch and none). Ping-pong's memoised candidate 0 is random proposals' cost, so the two variants must
+// give the same bits; derp_debug_sees evaluates both through this helper.
+template <bool RANDOM>
+constexpr int cost_sees_lean() {
+  return (DERP_LEAN_PROJ != 0) * ((DERP_ATAN_LUT ? 2 : 1) + (RANDOM ? 4 : 0));
+}
+
 template <bool SCALAR = false, bool RANDOM = false, bool RELOAD_RAY = false>
 __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int own, const PixCtx& px, float disparity,
                                                LdsPairs& pairs, unsigned& nPair, unsigned cull = 0, unsigned pix = 0,
@@ -891,9 +900,8 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
       pn.y = 0.5 + 0.45 * (double)(fy - floorf(fy) - 0.5f);
       const bool vis = (s & 1) != 0;
 #else
-      // (bit 2: square roots through sqrt_lean — random proposals, where its three registers decide between scratch and none)
-      const bool vis = sees<(DERP_LEAN_PROJ != 0) * ((DERP_ATAN_LUT ? 2 : 1) + (RANDOM ? 4 : 0))>(cs, pWorld, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1],
-                                                 1.0, 1.0, pn, pairs.atanLut);
+      const bool vis = sees<cost_sees_lean<RANDOM>()>(cs, pWorld, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1],
+                                                      1.0, 1.0, pn, pairs.atanLut);
 #endif
       if (__ballot(pend) != 0ull) {
         consume();
@@ -1050,6 +1058,51 @@ __global__ void k_debug_atan2_ypos(const double* __restrict__ y, const double* _
     const double a = atan2_ypos(y[i], x[i]);
     const double b = atan2_ypos_lut(y[i], x[i], atanLut);
     out[i] = (__double_as_longlong(a) == __double_as_longlong(b)) ? (DERP_ATAN_LUT ? b : a) : __builtin_nan("");
+  }
+#endif
+}
+
+// the fp64 primitives of the projection on device-memory arguments (nothing constant-folds): op 0 sqrt_lean(a), 1 sqrt(a),
+// 2 div_plain(a, b), 3 a / b
+__global__ void k_debug_fp64(int op, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out,
+                             size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+#if defined(__HIP_DEVICE_COMPILE__)
+  for (; i < n; i += step) {
+    const double x = a[i], y = b[i];
+    out[i] = op == 0 ? sqrt_lean(x) : op == 1 ? sqrt(x) : op == 2 ? div_plain(x, y) : x / y;
+  }
+#endif
+}
+
+// Camera::sees of source camera `src` exactly as the cost kernels evaluate it (the normalised camera, res 1, the atan table
+// in LDS): out[6 i ..] = (vis, pix.x, pix.y) of the ping-pong / brute-force variant, then of the random-proposal variant.
+// A pixel `sees` leaves untouched (outside the FOV cone) reads NaN.
+__global__ void k_debug_sees(const Cam* __restrict__ cams, int src, const double* __restrict__ xyz, double* __restrict__ out,
+                             size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ double atanLut[kAtanLutDoubles];
+  atan_lut_fill(atanLut);
+  __syncthreads();
+  const double* lut = (DERP_ATAN_LUT && DERP_LEAN_PROJ) ? atanLut : nullptr;
+  const Cam& cs = cams[src];
+  for (; i < n; i += step) {
+    const D3 p = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    D2 a = {__builtin_nan(""), __builtin_nan("")}, b = a;
+    const bool va = sees<cost_sees_lean<false>()>(cs, p, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1], 1.0, 1.0,
+                                                  a, lut);
+    const bool vb = sees<cost_sees_lean<true>()>(cs, p, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1], 1.0, 1.0,
+                                                 b, lut);
+    double* o = out + 6 * i;
+    o[0] = va ? 1.0 : 0.0;
+    o[1] = a.x;
+    o[2] = a.y;
+    o[3] = vb ? 1.0 : 0.0;
+    o[4] = b.x;
+    o[5] = b.y;
   }
 #endif
 }

@@ -98,7 +98,7 @@ EXPORTS = [
     "derp_level_begin", "derp_stage_reproject_colors", "derp_stage_brute_force", "derp_stage_random_proposals",
     "derp_stage_ping_pong", "derp_stage_mismatches", "derp_stage_bilateral_filter", "derp_stage_median_filter", "derp_stage_mask_fov",
     "derp_level_end", "derp_set_level_disparity", "derp_get_level_disparity", "derp_cost_map", "derp_debug_download",
-    "derp_debug_atan2_ypos",
+    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees",
     "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
     "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
     "derp_render_vertices",
@@ -389,6 +389,25 @@ class Derp:
         out = np.zeros_like(y)
         self._ck(lib().derp_debug_atan2_ypos(self.h, _p(y), _p(x), _p(out), C.c_size_t(y.size)))
         return out
+
+    FP64_OPS = {"sqrt_lean": 0, "sqrt": 1, "div_plain": 2, "div": 3}
+
+    def debug_fp64(self, op, a, b=None):
+        """One of the cost kernels' fp64 primitives (FP64_OPS) evaluated on the device, element by element."""
+        a = np.ascontiguousarray(a, np.float64)
+        b = None if b is None else np.ascontiguousarray(b, np.float64)
+        assert b is None or b.shape == a.shape
+        out = np.zeros_like(a)
+        self._ck(lib().derp_debug_fp64(self.h, self.FP64_OPS[op], _p(a), _p(b), _p(out), C.c_size_t(a.size)))
+        return out
+
+    def debug_sees(self, src, xyz):
+        """Camera::sees of source camera `src` as the cost kernels evaluate it -> (vis [2, n] bool, pix [2, n, 2] f64):
+        row 0 the ping-pong / brute-force variant, row 1 the random-proposal variant (NaN pixels outside the FOV cone)."""
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        out = np.zeros((len(xyz), 2, 3))
+        self._ck(lib().derp_debug_sees(self.h, src, _p(xyz), C.c_size_t(len(xyz)), _p(out)))
+        return out[:, :, 0].T != 0, np.ascontiguousarray(out[:, :, 1:].transpose(1, 0, 2))
 
     def debug(self, d, s, which):
         h, w = self._shape(self._cur)

@@ -192,6 +192,13 @@ int derp_debug_download(derp_ctx* ctx, int dst, int src, int which, void* out);
 /* the cost kernels' own fp64 atan2 (FTHETA branch of Camera::cameraToSensor, Camera.h:306-309): out[i] =
  * atan2(y[i], x[i]) for y >= 0, as the device routine computes it — so that a test can hold it against libm */
 int derp_debug_atan2_ypos(derp_ctx* ctx, const double* y, const double* x, double* out, size_t n);
+/* the cost kernels' fp64 primitives on the device: out[i] = op 0 sqrt_lean(a[i]), 1 sqrt(a[i]), 2 div_plain(a[i], b[i]),
+ * 3 a[i] / b[i] (the compiler's division); b may be null for ops 0 and 1 */
+int derp_debug_fp64(derp_ctx* ctx, int op, const double* a, const double* b, double* out, size_t n);
+/* Camera::sees (Camera.h:184-190) of source camera `src`, as the cost kernels evaluate it (normalised camera, res 1):
+ * out[6 i .. 6 i + 5] = (vis, pix.x, pix.y) of the ping-pong / brute-force variant, then of the random-proposal variant,
+ * for the rig points xyz[3 i .. 3 i + 2]; pix is NaN where the point lies outside the FOV cone */
+int derp_debug_sees(derp_ctx* ctx, int src, const double* xyz, size_t n, double* out);
 
 /* mismatch mask of the level processed last (dstMismatchedDisparityMask, PyramidLevel.h:332-338) */
 int derp_download_mismatch_mask(derp_ctx* ctx, int dst, uint8_t* out);

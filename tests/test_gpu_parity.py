@@ -990,37 +990,7 @@ def test_rephotography_score(small, gpu):
             assert 0.2 < (ref[..., 3] > 0).mean() <= 1.0
 
 
-def _mixed_type_rig(res):
-    """Six cameras on a 40-degree arc, two each RECTILINEAR / EQUISOLID / ORTHOGRAPHIC plus FTHETA
-    neighbours, some with and some without distortion and explicit fov (Camera.h:301-378)."""
-    import math
-
-    from facebook360_dep_amd import synth
-
-    base = synth.make_rig(6, res, layout="arc")["cameras"]
-    spec = [
-        ("RECTILINEAR", 0.50, 0.75, (-0.02, 0.001, 0.0)),
-        ("FTHETA", 0.36, math.pi / 2, synth.DISTORTION),
-        ("EQUISOLID", 0.36, 1.4, (0.0, 0.0, 0.0)),
-        ("ORTHOGRAPHIC", 0.52, 1.2, (0.01, 0.0, 0.0)),
-        ("RECTILINEAR", 0.55, None, (0.0, 0.0, 0.0)),
-        ("EQUISOLID", 0.40, None, (-0.01, 0.002, -0.0005)),
-    ]
-    cams = []
-    for i, (cam, (kind, f, fov, dist)) in enumerate(zip(base, spec)):
-        az = math.radians(-20.0 + 8.0 * i)
-        fwd = np.array([math.cos(az), math.sin(az), 0.05 * ((i % 2) * 2 - 1)])
-        fw, up, right = synth._frame(fwd)
-        cam = dict(cam, type=kind, focal=[f * res, -f * res], forward=fw.tolist(), up=up.tolist(),
-                   right=right.tolist(), origin=(0.25 * fw).tolist())
-        cam.pop("fov", None)
-        cam.pop("distortion", None)
-        if fov is not None:
-            cam["fov"] = fov
-        if any(dist):
-            cam["distortion"] = list(dist)
-        cams.append(cam)
-    return {"cameras": cams}
+_mixed_type_rig = common.mixed_type_rig
 
 
 def test_canopy_cubemap(built):
