@@ -2330,6 +2330,12 @@ __device__ __forceinline__ float div_by_const(float y, double rcp) {
   return (float)((double)y * rcp);
 }
 
+// The same for an integer numerator that fp32 holds exactly (|y| < 2^24): (float)y / d with (float)y == y, so the
+// conversion to fp64 can start from the integer and the operands of the quotient are the same numbers.
+__device__ __forceinline__ float div_int_by_const(int y, double rcp) {
+  return (float)((double)y * rcp);
+}
+
 // `tab` = kExp2fTab staged in LDS by the caller (a divergent __constant__ index would be a global load per call)
 __device__ __forceinline__ float expf_glibc(float x, const unsigned long long* tab) {
   const double InvLn2N = 0x1.71547652b82fep+0 * 32;
@@ -2971,6 +2977,7 @@ __global__ void k_temporal(TemporalFrames F, int W, int H, float sigma, int radi
   const ushort4 ref = F.refGuide[pg + idx];
   const float sig2 = sigma * sigma;
   const double rcpSig2 = 1.0 / (double)sig2;
+  const double rcp65535 = 1.0 / 65535.0;
   float weightedSumPix = 0.f, sumWeight = 0.f;
   if (!F.first) {
     const float2 acc = F.carry[pd + idx];
@@ -2990,9 +2997,9 @@ __global__ void k_temporal(TemporalFrames F, int W, int H, float sigma, int radi
           continue;
         }
         const ushort4 sc = guide[j];
-        const float e0 = (float)((int)ref.x - (int)sc.x) / 65535.0f;
-        const float e1 = (float)((int)ref.y - (int)sc.y) / 65535.0f;
-        const float e2 = (float)((int)ref.z - (int)sc.z) / 65535.0f;
+        const float e0 = div_int_by_const((int)ref.x - (int)sc.x, rcp65535);  // (float)diff / 65535.0f
+        const float e1 = div_int_by_const((int)ref.y - (int)sc.y, rcp65535);  // (float)diff / 65535.0f
+        const float e2 = div_int_by_const((int)ref.z - (int)sc.z, rcp65535);  // (float)diff / 65535.0f
         const float weightedDiff = weight0 * (e0 * e0) + weight1 * (e1 * e1) + weight2 * (e2 * e2);
         const float weight = expf_glibc(div_by_const(-weightedDiff, rcpSig2), expTab);  // -weightedDiff / sig2
         weightedSumPix += centre * weight;
@@ -3042,25 +3049,72 @@ __global__ void __launch_bounds__(256)
   }
   const float sig2 = sigma * sigma;
   const double rcpSig2 = 1.0 / (double)sig2;
-  for (int t = 0; t < F.n; ++t) {
+  const double rcp65535 = 1.0 / 65535.0;
+  // Software pipeline over the window: the cells of frame t + 1 (the first two per thread: every cell up to radius 2)
+  // and its centre value are loaded into registers before the taps of frame t run and stored to the other buffer after
+  // them, so the global-load latency hides behind the taps. Guide texels are loaded whether or not their mask byte is
+  // set (clamped coordinates: always in bounds; a masked cell is never read back), which also takes the mask -> guide
+  // dependency out of the load. A tile with more than 512 cells loads the rest after the taps, unpipelined.
+  int cellSrc[2];  // source pixel of the thread's prefetched cells (the same for every frame)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int k = min(tid + i * 256, cells - 1);
+    const int ty = k / TW, tx = k - ty * TW;
+    const int sx = min(max(x0 - radius + tx, 0), W - 1), sy = min(max(y0 - radius + ty, 0), H - 1);
+    cellSrc[i] = sy * W + sx;
+  }
+  ushort4 nextG[2];
+  unsigned char nextM[2];
+  float centreNext = 0.f;
+  auto fetch = [&](int t) {
+    const uint8_t* __restrict__ mask = F.masks[t] + pd;
+    const ushort4* __restrict__ guide = F.guides[t] + pg;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      nextM[i] = mask[cellSrc[i]];
+      nextG[i] = guide[cellSrc[i]];
+    }
+    if (active) {
+      centreNext = F.images[t][pd + idx];
+    }
+  };
+  auto stash = [&](int t) {
     unsigned char* buf = ldsTemporal + (size_t)(t & 1) * bufBytes;
     ushort4* tg = reinterpret_cast<ushort4*>(buf);
     unsigned char* tm = buf + (size_t)cells * 8;
-    const uint8_t* __restrict__ mask = F.masks[t] + pd;
-    const ushort4* __restrict__ guide = F.guides[t] + pg;
-    for (int k = tid; k < cells; k += 256) {
-      const int ty = k / TW, tx = k - ty * TW;
-      const int sx = min(max(x0 - radius + tx, 0), W - 1), sy = min(max(y0 - radius + ty, 0), H - 1);
-      const size_t j = (size_t)sy * W + sx;
-      const unsigned char m = mask[j];
-      tm[k] = m;
-      if (m) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = tid + i * 256;
+      if (k < cells) {
+        tm[k] = nextM[i];
+        tg[k] = nextG[i];
+      }
+    }
+    if (cells > 512) {
+      const uint8_t* __restrict__ mask = F.masks[t] + pd;
+      const ushort4* __restrict__ guide = F.guides[t] + pg;
+      for (int k = tid + 512; k < cells; k += 256) {
+        const int ty = k / TW, tx = k - ty * TW;
+        const int sx = min(max(x0 - radius + tx, 0), W - 1), sy = min(max(y0 - radius + ty, 0), H - 1);
+        const size_t j = (size_t)sy * W + sx;
+        tm[k] = mask[j];
         tg[k] = guide[j];
       }
     }
+  };
+  fetch(0);
+  stash(0);
+  for (int t = 0; t < F.n; ++t) {
+    const unsigned char* buf = ldsTemporal + (size_t)(t & 1) * bufBytes;
+    const ushort4* tg = reinterpret_cast<const ushort4*>(buf);
+    const unsigned char* tm = buf + (size_t)cells * 8;
+    const float centre = centreNext;
+    // frame t's buffer is complete, and everyone has finished the taps of frame t - 1: its buffer takes frame t + 1
     __syncthreads();
+    if (t + 1 < F.n) {
+      fetch(t + 1);
+    }
     if (active) {
-      const float centre = F.images[t][pd + idx];
       for (int u = -radius; u <= radius; ++u) {
         for (int v = -radius; v <= radius; ++v) {
           const int k = ((int)threadIdx.y + radius + v) * TW + (int)threadIdx.x + radius + u;
@@ -3068,9 +3122,9 @@ __global__ void __launch_bounds__(256)
             continue;
           }
           const ushort4 sc = tg[k];
-          const float e0 = (float)((int)ref.x - (int)sc.x) / 65535.0f;
-          const float e1 = (float)((int)ref.y - (int)sc.y) / 65535.0f;
-          const float e2 = (float)((int)ref.z - (int)sc.z) / 65535.0f;
+          const float e0 = div_int_by_const((int)ref.x - (int)sc.x, rcp65535);  // (float)diff / 65535.0f
+          const float e1 = div_int_by_const((int)ref.y - (int)sc.y, rcp65535);  // (float)diff / 65535.0f
+          const float e2 = div_int_by_const((int)ref.z - (int)sc.z, rcp65535);  // (float)diff / 65535.0f
           const float weightedDiff = weight0 * (e0 * e0) + weight1 * (e1 * e1) + weight2 * (e2 * e2);
           const float weight = expf_glibc(div_by_const(-weightedDiff, rcpSig2), expTab);  // -weightedDiff / sig2
           weightedSumPix += centre * weight;
@@ -3078,7 +3132,9 @@ __global__ void __launch_bounds__(256)
         }
       }
     }
-    // the buffer written next (t + 1) is the one read at t - 1: everyone passed this frame's barrier after reading it
+    if (t + 1 < F.n) {
+      stash(t + 1);
+    }
   }
   if (!inside) {
     return;
