@@ -542,9 +542,6 @@ int upsample_masked_dev(derp_ctx* c, const float* in, const uint8_t* mask, int s
 // Stored inverse warps (projWarpInv) are needed only for sources that are not the own source of a destination of the
 // same batch: everywhere else projWarpInv(d, s) is projWarp(ds, own(d)) (derp_kernels.h, batch_dst_of_source).
 bool batch_needs_inverse_warps(const derp_ctx* c, int dst0, int nd) {
-  if (DERP_NO_WARP_IDENTITY) {
-    return true;
-  }
   std::vector<char> covered(c->S, 0);
   for (int d = dst0; d < dst0 + nd; ++d) {
     covered[c->dst2srcH[d]] = 1;
@@ -624,12 +621,12 @@ int build_color_tables(derp_ctx* c, int dst0, int nd) {
 
 // number of cost-kernel blocks covering a W x H image (16x16 super-tiles of four 8x8 wave tiles)
 int tiles_of(int W, int H, int& tilesX) {
-  constexpr int B = DERP_TILE_BLOCK > 1 ? DERP_TILE_BLOCK : 1;  // tile grid padded to whole B x B squares
+  constexpr int B = kTileBlock;  // tile grid padded to whole B x B squares
   tilesX = ((W + 15) / 16 + B - 1) / B * B;
   const int tilesY = ((H + 15) / 16 + B - 1) / B * B;
-  return tilesX * tilesY * (256 / DERP_COST_BLOCK);
+  return tilesX * tilesY * (256 / kCostBlock);
 }
-constexpr size_t kCostLdsPerSrc = (size_t)DERP_COST_BLOCK * sizeof(SsdPair);
+constexpr size_t kCostLdsPerSrc = (size_t)kCostBlock * sizeof(SsdPair);
 int round8(int n) {
   return (n + 7) / 8 * 8;
 }
@@ -642,7 +639,7 @@ size_t lds_for_waves(size_t needed, int waves, size_t ldsPerCu, size_t fixed) {
   const size_t perBlock = ldsPerCu / (size_t)(4 * waves + 1) + 256;  // 4 * waves blocks fit, 4 * waves + 1 do not
   return std::max(needed, perBlock > fixed ? perBlock - fixed : needed);
 }
-constexpr size_t kCostLdsStatic = sizeof(PatchWin) * (DERP_COST_BLOCK / 64) + kAtanLutDoubles * sizeof(double);
+constexpr size_t kCostLdsStatic = sizeof(PatchWin) * (kCostBlock / 64) + kAtanLutDoubles * sizeof(double);
 // Which register budget of the two cost kernels to launch (k_ping_pong / k_random_proposals vs their _w3 twins): four waves
 // per SIMD need sixteen one-wave blocks per CU, i.e. LDS for sixteen — true up to 16 cameras (9.3 KB each of 160 KB; measured
 // 3.9 resident waves), not beyond (24 cameras: 13.3 KB, twelve blocks). DERP_COST_WAVES=3 / 4 forces one (developer A/B).
@@ -667,7 +664,7 @@ int run_brute_force(derp_ctx* c, int dst0, int nd) {
   const int tilesX = std::max(1, (V.W - 2 + 7) / 8), tilesY = std::max(1, (V.H - 2 + 7) / 8);
   const int tiles = tilesX * tilesY;
   const size_t lds = kCostLdsPerSrc * (size_t)(c->S);
-  hipLaunchKernelGGL(k_brute_costs, dim3(tiles, kNumDepths, nd), dim3(DERP_COST_BLOCK), lds, c->stream, V,
+  hipLaunchKernelGGL(k_brute_costs, dim3(tiles, kNumDepths, nd), dim3(kCostBlock), lds, c->stream, V,
                      c->bruteCost.as<float>(), c->bruteConf.as<float>(), tilesX, tiles);
   KCHECK(c);
   hipLaunchKernelGGL(k_brute_select, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->bruteCost.as<float>(),
@@ -694,7 +691,7 @@ int run_random_proposals(derp_ctx* c, int dst0, int nd) {
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->randomWaves, c->ldsPerCu, kCostLdsStatic);
   hipLaunchKernelGGL(cost_four_waves(c) ? k_random_proposals : k_random_proposals_w3, dim3(round8(tiles), nd),
-                     dim3(DERP_COST_BLOCK), lds, c->stream, V, c->rank.as<int>(), tilesX, tiles);
+                     dim3(kCostBlock), lds, c->stream, V, c->rank.as<int>(), tilesX, tiles);
   KCHECK(c);
   return 0;
 }
@@ -714,7 +711,7 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   const bool four = cost_four_waves(c);
   const auto kernel = c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3);
   for (int it = 1; it <= c->opt.ping_pong_iterations; ++it) {
-    hipLaunchKernelGGL(kernel, dim3(round8(tiles), nd), dim3(DERP_COST_BLOCK), lds,
+    hipLaunchKernelGGL(kernel, dim3(round8(tiles), nd), dim3(kCostBlock), lds,
                        c->stream, V, c->changed.as<uint8_t>(), c->dispRes.as<float>(), c->costRes.as<float>(), tilesX,
                        (int)(it == 1 && c->randomRanThisLevel && !c->noMemo));
     KCHECK(c);
@@ -1988,7 +1985,7 @@ int derp_cost_map(derp_ctx* c, int d, const float* disp, float* cost, float* con
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = kCostLdsPerSrc * (size_t)(c->S);
-  hipLaunchKernelGGL(k_cost_map, dim3(tiles), dim3(DERP_COST_BLOCK), lds, c->stream, V, d, c->staging.as<float>(),
+  hipLaunchKernelGGL(k_cost_map, dim3(tiles), dim3(kCostBlock), lds, c->stream, V, d, c->staging.as<float>(),
                      c->stagingB.as<float>(), c->stagingB.as<float>() + n, tilesX);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -28,100 +28,32 @@
 
 namespace derp {
 
-// waves per SIMD the register allocator must leave room for (__launch_bounds__). Round 6: FOUR for every cost kernel
-// (<= 128 VGPRs) — the destination patch lives in LDS (PatchWin), the 4x4 block is streamed by columns (no parked sums),
-// and the candidate loops carry a handful of values. Rounds 2-5 ran three (164-167 VGPRs), an odd count at which a plain
-// fp32 op costs 2.8 instead of 2.08 cycles (tools/valu_ubench.hip). Measured on one box (profiles/r06_kernel_variants.txt):
-// level-0 ping-pong 59.8 -> 55.0 ms, random proposals 42.3 -> 39.9 ms per frame; the same sources held to three waves:
-// 61.8 / 42.0. What still spills at 128 is cold: a few per-pixel / per-candidate values around the source loops.
+// Compile-time switches that something outside this header still builds with (everything else the earlier rounds tried
+// is settled and folded into the code; DESIGN.md sections 6 and 9 keep the measurements).
+// waves per SIMD the register allocator must leave room for (__launch_bounds__); 3 = the A/B against three waves
 #ifndef DERP_COST_MIN_WAVES
 #define DERP_COST_MIN_WAVES 4
 #endif
 #ifndef DERP_RANDOM_MIN_WAVES
 #define DERP_RANDOM_MIN_WAVES 4
 #endif
-#ifndef DERP_COST_BLOCK
-#define DERP_COST_BLOCK 64
-#endif
-#ifndef DERP_TILE_BLOCK
-#define DERP_TILE_BLOCK 4
-#endif
-// skip, per wave, the sources that face away from the wave's pixels for every candidate depth (behind_sources)
-#ifndef DERP_SOURCE_CULL
-#define DERP_SOURCE_CULL 1
-#endif
-// fp64 atan2 / division of the cost kernels' projection through the short routines of derp_camera.h (0 = the
-// device library's)
-#ifndef DERP_LEAN_PROJ
-#define DERP_LEAN_PROJ 1
-#endif
-// the short atan2's per-interval constants from a table in LDS (1) or from scalar literals chosen by branching (0)
-#ifndef DERP_ATAN_LUT
-#define DERP_ATAN_LUT 1
-#endif
-// tools/valu_model.py only (never a product build): compile the cost kernels without their cold paths — the
-// tap-by-tap SSD fallback and the non-FTHETA camera types — so that the static instruction mix it weights the
-// typed VALU counters with is the mix of the hot loops
-#ifndef DERP_MIX_HOT_ONLY
-#define DERP_MIX_HOT_ONLY 0
-#endif
-// computeSSD's 4x4-block arithmetic in plain fp32 (1) or packed fp32 (0), per kernel family
-// random proposals: each XCD walks its own band of tiles (1, like the coherent kernels) or all XCDs sweep the image
-// together (0: consecutive blocks, which the hardware deals round-robin to the XCDs, are neighbouring tiles)
-#ifndef DERP_RANDOM_SWIZZLE
-#define DERP_RANDOM_SWIZZLE 1
-#endif
-#ifndef DERP_RANDOM_SSD_SCALAR
-#define DERP_RANDOM_SSD_SCALAR 1
-#endif
-#ifndef DERP_COST_SSD_SCALAR
-#define DERP_COST_SSD_SCALAR 0
-#endif
-// random proposals, round 5: every lane of a wave gathers at its own place on its epipolar curve; the kernel's
-// gathers miss L2 (66 % hits, 141 GB through the memory-side counters per level-0 launch at config 2 in round 4).
-//  DERP_RANDOM_BLOCK_BIAS (on)  srcBias = bilinear sample of projBias = 2x2 taps of the 3x3 box of projColor — which are
-//                        sums over exactly the 4x4 block already in registers: the two projBias loads (2.1 cache lines
-//                        per pair, and a third of the kernel's table footprint) become ~110 VALU instructions. Exact:
-//                        the box is an integer sum < 2^24 (exact in fp32) and trunc((s + 4) * fl(1/9)) == (s + 4) / 9
-//                        for every s <= 9 * 65535 (checked exhaustively, tests/test_abi.py). Taps on the image's first /
-//                        last row or column (BORDER_REFLECT_101 there, a replicated ring in the table) load projBias.
-//                        Measured (profiles/r05_kernel_variants.txt): 142 -> 53 GB per launch, L2 hits 66 -> 82 %,
-//                        config 4's random proposals 485 -> 367 ms.
-//  DERP_RANDOM_TILED (off: measured, rejected)  the 4x4 block from a second copy of projColor stored in 4x4-texel tiles
-//                        of one 128-byte line each (k_reproject_bias writes both): 3.06 lines per block instead of
-//                        4.75, but sixteen 8-byte loads instead of eight 16-byte ones. 53 -> 48 GB, and slower: +2 %
-//                        at config 2; at config 4 the copy costs a third destination batch (+25 % table bytes) and the
-//                        tiled stores +25 ms of k_reproject_bias.
+// random proposals read the 4x4 block from a second copy of projColor stored in 4x4-texel tiles (projColorT); measured
+// and rejected at 2048^2, kept compilable for the A/B at 4096^2
 #ifndef DERP_RANDOM_TILED
 #define DERP_RANDOM_TILED 0
 #endif
-#ifndef DERP_RANDOM_BLOCK_BIAS
-#define DERP_RANDOM_BLOCK_BIAS 1
+// tools/valu_model.py: the cost kernels without their cold paths (tap-by-tap SSD fallback, non-FTHETA camera types)
+#ifndef DERP_MIX_HOT_ONLY
+#define DERP_MIX_HOT_ONLY 0
 #endif
-// ping-pong: read the pixel's ray direction from its table per candidate instead of keeping it (in scratch) across the loop
-#ifndef DERP_PP_RELOAD_RAY
-#define DERP_PP_RELOAD_RAY 1
+// tools/phase_timers.py: wave cycles per phase of computeCost in the counter slots (1 | 2, see PhaseTimers)
+#ifndef DERP_PHASE_TIMERS
+#define DERP_PHASE_TIMERS 0
 #endif
-// a wave whose lanes are all in computeSSD's exact case runs a copy of the 4x4-block arithmetic specialised for it
-#ifndef DERP_UNIFORM_WEIGHTS
-#define DERP_UNIFORM_WEIGHTS 1
-#endif
-// ... also of the plain-fp32 form (random proposals): + 7 VGPRs there, i.e. the third wave unless they are found elsewhere
-#ifndef DERP_UNIFORM_WEIGHTS_SCALAR
-#define DERP_UNIFORM_WEIGHTS_SCALAR 0
-#endif
-// random proposals: the same (round 6: six registers the fourth wave needs)
-#ifndef DERP_RANDOM_RELOAD_RAY
-#define DERP_RANDOM_RELOAD_RAY 1
-#endif
-#ifndef DERP_RANDOM_RECONVERT
-#define DERP_RANDOM_RECONVERT 1
-#endif
-// developer A/B: 1 = compute and store every inverse warp (round 4) instead of reading projWarp(ds, own) where source s
-// is a destination of the batch
-#ifndef DERP_NO_WARP_IDENTITY
-#define DERP_NO_WARP_IDENTITY 0
-#endif
+// DERP_COUNT_UNION (tools/union_probe.py): counter slots [2] / [3] hold the SSD iterations the waves walk
+// DERP_COUNT_PP_FILL (tools/pp_fill_probe.py): ping-pong's counter slot [1] holds the lane-slots its waves walk
+static constexpr int kCostBlock = 64;  // threads per cost-kernel block: ONE wave (tile_pixel)
+static constexpr int kTileBlock = 4;   // super-tiles are walked in kTileBlock x kTileBlock squares (tile_pixel)
 static constexpr int kPadW = 1;   // ring of projWarp
 static constexpr int kPadC = 2;   // ring of projColor / projBias
 static constexpr int kMaxSrc = 32;
@@ -207,16 +139,16 @@ __device__ __forceinline__ int xcd_swizzle(int b, int n, int rot) {
 
 // Pixel handled by this thread. A wave owns an 8x8 pixel tile; four consecutive waves form a 16x16
 // super-tile (raster order over super-tiles). `item` numbers the blocks of the launch; a block holds
-// blockDim.x / 64 consecutive waves. Cost kernels run ONE wave per block (DERP_COST_BLOCK = 64): the
+// blockDim.x / 64 consecutive waves. Cost kernels run ONE wave per block (kCostBlock = 64): the
 // waves of a pixel tile finish at very different times, and a single-wave block frees its slot at once.
 __device__ __forceinline__ void tile_pixel(int item, int tilesX, int& x, int& y) {
   const int lane = threadIdx.x & 63;
   const int gw = item * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
   const int super = gw >> 2, quad = gw & 3;
-  // super-tiles are walked in DERP_TILE_BLOCK x DERP_TILE_BLOCK squares (128 x 128 px for 8): the tiles an
+  // super-tiles are walked in kTileBlock x kTileBlock squares (64 x 64 px): the tiles an
   // XCD works on at one time then cover a compact square instead of a 16-px-high strip, which shrinks
   // the union of the source-image footprints their gathers fall into (tilesX is padded to the block size)
-  constexpr int B = DERP_TILE_BLOCK;
+  constexpr int B = kTileBlock;
   const int blk = super / (B * B), in = super % (B * B);
   const int blocksX = tilesX / B;
   const int tx = (blk % blocksX) * B + (in % B), ty = (blk / blocksX) * B + (in / B);
@@ -302,7 +234,7 @@ __device__ __forceinline__ void patch_window_fill(const LevelView& V, int own, i
 struct LdsPairs {
   SsdPair* base;
   int stride;
-  const double* atanLut;  // atan_lut_fill's table, or null: select the constants from scalar literals
+  const double* atanLut;  // atan_lut_fill's table
   __device__ __forceinline__ SsdPair get(int i) const {
     return base[i * stride];
   }
@@ -310,6 +242,26 @@ struct LdsPairs {
     base[i * stride] = v;
   }
 };
+
+// What every cost wave sets up before anything diverges, all 64 lanes taking part: its 10x10 window of destination
+// colours (PatchWin) around its 8x8 tile, whose first pixel is (x0, y0), the atan table of the projection, and the lane's
+// column of the pair slots (the kernel's dynamic LDS); the barrier publishes the two tables. (The callers subtract the
+// lane's place in the tile themselves: the compacted ping-pong loop needs the same difference again.)
+__device__ __forceinline__ LdsPairs cost_wave_prologue(const LevelView& V, int d, int x0, int y0, PatchWin*& win) {
+  extern __shared__ SsdPair ldsPairs[];
+  __shared__ PatchWin patchWin[kCostBlock / 64];
+  win = &patchWin[threadIdx.x >> 6];
+  patch_window_fill(V, V.dst2src[d], x0, y0, win);
+#if defined(__HIP_DEVICE_COMPILE__)  // (the table's routines exist in the device pass only)
+  __shared__ double atanLut[kAtanLutDoubles];
+  atan_lut_fill(atanLut);
+  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
+#else
+  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
+#endif
+  __syncthreads();
+  return pairs;
+}
 
 // The texels one computeSSD call reads, requested ahead of the arithmetic: the 4x4 block of projColor
 // around round(x, y) (rows yi-2..yi+1, cols xi-2..xi+1) and the 2x2 bias taps, as ten 16-byte loads. The
@@ -322,7 +274,7 @@ struct SsdTexels {
 // The random-proposal form: the block from the tiled copy `colT` (sixteen 8-byte loads: a texel row of the block can
 // straddle two tiles), the bias taps only for lanes whose taps touch the image's first / last row or column
 // (`border`; everywhere else ssd_arith sums them from the block).
-template <bool TILED, bool BLOCK_BIAS>
+template <bool TILED>
 __device__ __forceinline__ void ssd_issue_random(const LevelView& V, const ushort4* __restrict__ col, const ushort4* __restrict__ colT,
                                                  const ushort4* __restrict__ bia, float xDstSrc, float yDstSrc, SsdTexels& T,
                                                  bool& border) {
@@ -362,7 +314,7 @@ __device__ __forceinline__ void ssd_issue_random(const LevelView& V, const ushor
   }
   // bias taps (xi - 1 .. xi, yi - 1 .. yi): their 3x3 boxes lie inside the image — where the table's box (BORDER_REFLECT_101)
   // and the block's (replicated ring) are the same nine texels — iff 2 <= xi <= W - 2 and 2 <= yi <= H - 2
-  border = !BLOCK_BIAS || xi < 2 || yi < 2 || xi > V.W - 2 || yi > V.H - 2;
+  border = xi < 2 || yi < 2 || xi > V.W - 2 || yi > V.H - 2;
   T.ba = T.bb = (u4a8){0u, 0u, 0u, 0u};
   if (border) {
     const unsigned boff = off + ((unsigned)pitch + 1u) * 8u;  // (yi - 1, xi - 1)
@@ -384,11 +336,6 @@ __device__ __forceinline__ void ssd_issue(const LevelView& V, const ushort4* __r
     T.raw[row][0] = *reinterpret_cast<const u4a8*>(base + (off + (unsigned)row * (unsigned)pitch * 8u));
     T.raw[row][1] = *reinterpret_cast<const u4a8*>(base + (off + (unsigned)row * (unsigned)pitch * 8u + 16u));
   }
-#ifdef DERP_ABLATE_NO_BIAS_LOAD  // developer ablation: same arithmetic, two loads fewer (results are wrong)
-  T.ba = T.raw[1][0];
-  T.bb = T.raw[2][0];
-  return;
-#endif
   const unsigned boff = off + ((unsigned)pitch + 1u) * 8u;  // (yi - 1, xi - 1)
   const char* bbase = reinterpret_cast<const char*>(bia);
   T.ba = *reinterpret_cast<const u4a8*>(bbase + boff);
@@ -396,23 +343,13 @@ __device__ __forceinline__ void ssd_issue(const LevelView& V, const ushort4* __r
 }
 
 // computeSSD (DerpUtil.cpp:126-162) for one source whose projected tables are `col` / `bias`; `T` holds the
-// texels ssd_issue requested for (xDstSrc, yDstSrc).
-template <bool SCALAR, bool BLOCK_BIAS = false>
+// texels ssd_issue requested for (xDstSrc, yDstSrc). Two shapes:
+//  RANDOM = false (ping-pong, brute force, cost map): srcBias from the projBias taps, the block in packed fp32;
+//  RANDOM = true  (random proposals, whose gathers miss L2): srcBias summed from the block already in registers instead of
+//                 two more loads (`border` lanes excepted, see ssd_issue_random), the block in plain fp32.
+template <bool RANDOM>
 __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& px, const ushort4* __restrict__ col,
                                              const SsdTexels& T, float xDstSrc, float yDstSrc, bool border = true) {
-#ifdef DERP_ABLATE_NO_SSD
-  return {xDstSrc * 1e-3f, yDstSrc * 1e-3f};
-#endif
-#ifdef DERP_ABLATE_SSD_LOADS_ONLY  // developer ablation: the ten loads stay, the arithmetic is a few xors
-  {
-    unsigned a = T.ba.x ^ T.bb.y, b = T.ba.z ^ T.bb.w;
-    for (int r = 0; r < 4; ++r) {
-      a ^= T.raw[r][0].x ^ T.raw[r][0].z ^ T.raw[r][1].x ^ T.raw[r][1].z;
-      b ^= T.raw[r][0].y ^ T.raw[r][0].w ^ T.raw[r][1].y ^ T.raw[r][1].w;
-    }
-    return {(float)(a & 0xffff) * 1e-3f + xDstSrc * 1e-3f, (float)(b & 0xffff) * 1e-3f + yDstSrc * 1e-3f};
-  }
-#endif
   const int pitch = V.W + 2 * kPadC;
   const u4a8 (&raw)[4][2] = T.raw;
   // texel (row r, column k) of the 4x4 block: the (B | G << 16) word and the R word
@@ -420,46 +357,16 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   auto word_r = [&](const u4a8 (&q)[4][2], int r, int k) { return (k & 1) ? q[r][k >> 1].w : q[r][k >> 1].y; };
   // --- srcBias = getPixelBilinear(dstSrcColorBias, xDstSrc, yDstSrc)
   float bias[3];
-  if constexpr (BLOCK_BIAS) {
+  const float bxf = roundf(xDstSrc), byf = roundf(yDstSrc);
+  const float bxw = xDstSrc - bxf + 0.5f, byw = yDstSrc - byf + 0.5f;
+  const float w00 = (1 - bxw) * (1 - byw), w01 = bxw * (1 - byw), w10 = (1 - bxw) * byw, w11 = bxw * byw;
+  if constexpr (RANDOM) {
     // The four taps are 3x3 boxes of projColor (colorBias, DerpUtil.cpp:208-210: cv::blur on CV_16UC3 = exact integer sum,
-    // round(s / 9)) over block columns 0..2 / 1..3 and rows 0..2 / 1..3. Columns are visited 3, 2, 1, 0 so that the floats
-    // of columns 1 and 0 are the ones the block arithmetic below starts with; columns 2 and 3 are converted again there
-    // (their words pass through an empty asm below: kept live instead, the 24 floats cost the kernel a wave).
-    const float xf = roundf(xDstSrc), yf = roundf(yDstSrc);
-    const float xw = xDstSrc - xf + 0.5f, yw = yDstSrc - yf + 0.5f;
-    const float w00 = (1 - xw) * (1 - yw), w01 = xw * (1 - yw), w10 = (1 - xw) * yw, w11 = xw * yw;
-    if constexpr (!SCALAR) {
-      // packed form: (B, G) of a texel as one register pair; R of (rows 0..2, rows 1..3) as one pair
-      v2f topBG[2], botBG[2], tbR[2];  // [tap column]
-#pragma unroll
-      for (int k = 3; k >= 0; --k) {
-        const v2f m = bg_of(word_bg(raw, 1, k)) + bg_of(word_bg(raw, 2, k));
-        const v2f vT = m + bg_of(word_bg(raw, 0, k)), vB = m + bg_of(word_bg(raw, 3, k));
-        const float mR = (float)(word_r(raw, 1, k) & 0xffff) + (float)(word_r(raw, 2, k) & 0xffff);
-        const v2f vR = splat2(mR) + (v2f){(float)(word_r(raw, 0, k) & 0xffff), (float)(word_r(raw, 3, k) & 0xffff)};
-        const v2f four = splat2(4.0f);  // first column of a box: start it at + 4 (round(s / 9) = (s + 4) / 9)
-        if (k == 3) {
-          topBG[1] = vT + four, botBG[1] = vB + four, tbR[1] = vR + four;
-        } else if (k == 2) {
-          topBG[1] += vT, botBG[1] += vB, tbR[1] += vR;
-          topBG[0] = vT + four, botBG[0] = vB + four, tbR[0] = vR + four;
-        } else if (k == 1) {
-          topBG[1] += vT, botBG[1] += vB, tbR[1] += vR;
-          topBG[0] += vT, botBG[0] += vB, tbR[0] += vR;
-        } else {
-          topBG[0] += vT, botBG[0] += vB, tbR[0] += vR;
-        }
-      }
-      const v2f ninth = splat2(1.0f / 9.0f);
-      const v2f t00 = trunc2(topBG[0] * ninth), t01 = trunc2(topBG[1] * ninth), t10 = trunc2(botBG[0] * ninth),
-                t11 = trunc2(botBG[1] * ninth);
-      const v2f r0 = trunc2(tbR[0] * ninth), r1 = trunc2(tbR[1] * ninth);  // (top, bottom) of tap column 0 / 1
-      const v2f sbBG = trunc2(splat2(w00) * t00 + splat2(w01) * t01 + splat2(w10) * t10 + splat2(w11) * t11);
-      const v2f bBG = px.dstBiasBG - sbBG;
-      bias[0] = bBG.x;
-      bias[1] = bBG.y;
-      bias[2] = px.dstBiasR - bilerp_u16(r0.x, r1.x, r0.y, r1.y, w00, w01, w10, w11);
-    } else {
+    // round(s / 9)) over block columns 0..2 / 1..3 and rows 0..2 / 1..3: sums over exactly the 4x4 block. Exact: a box is an
+    // integer sum < 2^24 and trunc((s + 4) * fl(1/9)) == (s + 4) / 9 for every s <= 9 * 65535 (tests/test_abi.py).
+    // Columns are visited 3, 2, 1, 0 so that the floats of columns 1 and 0 are the ones the block arithmetic below starts
+    // with; columns 2 and 3 are converted again there (their words pass through an empty asm below: kept live instead,
+    // the 24 floats cost the kernel a wave).
     float top[3][2], bot[3][2];  // [channel][tap column]: rows 0..2 and rows 1..3
 #pragma unroll
     for (int k = 3; k >= 0; --k) {
@@ -501,7 +408,6 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
       const float t10 = __builtin_truncf(bot[ch][0] * ninth), t11 = __builtin_truncf(bot[ch][1] * ninth);
       bias[ch] = px.dstBias(ch) - bilerp_u16(t00, t01, t10, t11, w00, w01, w10, w11);
     }
-    }
     if (__ballot(border) != 0ull) {  // taps on the image's rim: the table's values (loaded by ssd_issue_random)
       if (border) {
         const u4a8 a = T.ba, b = T.bb;
@@ -511,9 +417,6 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
       }
     }
   } else {
-    const float xf = roundf(xDstSrc), yf = roundf(yDstSrc);
-    const float xw = xDstSrc - xf + 0.5f, yw = yDstSrc - yf + 0.5f;
-    const float w00 = (1 - xw) * (1 - yw), w01 = xw * (1 - yw), w10 = (1 - xw) * yw, w11 = xw * yw;
     const u4a8 a = T.ba, b = T.bb;
     // (B, G) as one packed pair, R alone — same per-lane operations as bilerp_u16
     const v2f sbBG = trunc2(splat2(w00) * bg_of(a.x) + splat2(w01) * bg_of(a.z) + splat2(w10) * bg_of(b.x) +
@@ -531,14 +434,14 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   // registers until the end. Each operation is the same IEEE operation, in the same order, as the scalar expression it
   // replaces; the destination patch comes from the wave's LDS window (PixCtx).
   float first = 0.f, second = 0.f;
-  // (block bias: columns 2 and 3 were converted once already for the box sums; an opaque copy of their words makes the
+  // (random proposals: columns 2 and 3 were converted once already for the box sums; an opaque copy of their words makes the
   // compiler convert them again here instead of keeping 24 more floats alive across the bias arithmetic)
   u4a8 rawB[4][2];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     rawB[r][0] = raw[r][0];
     rawB[r][1] = raw[r][1];
-    if constexpr (BLOCK_BIAS && DERP_RANDOM_RECONVERT) {
+    if constexpr (RANDOM) {
       unsigned a = raw[r][1].x, b = raw[r][1].y, c = raw[r][1].z, d = raw[r][1].w;
       asm("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
       rawB[r][1] = (u4a8){a, b, c, d};
@@ -685,20 +588,16 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
     }
     regular = (xi[0] == xi[1] - 1) && (xi[2] == xi[1] + 1) && (yi[0] == yi[1] - 1) && (yi[2] == yi[1] + 1);
   }
-  if (DERP_UNIFORM_WEIGHTS && (!SCALAR || DERP_UNIFORM_WEIGHTS_SCALAR) && __ballot(!exact) == 0ull) {
+  if (!RANDOM && __ballot(!exact) == 0ull) {
     // every lane of the wave is in the exact case (all but ~1 % of the waves: x or y inside [2^k - 1, 2^k) or below 1
     // breaks it): ONE weight per axis serves the nine offsets, and this copy of the block says so at compile time —
     // the four weight products are formed once, and no values of the general path have to be merged in (three dozen
-    // register moves per call in the shared copy)
+    // register moves per call in the shared copy). Packed form only: a second copy of the plain form costs random
+    // proposals 7 VGPRs, i.e. their fourth wave.
     const float xwu[3] = {xw[1], xw[1], xw[1]};
-    if constexpr (SCALAR) {
-      const float ywu[3] = {yw[1], yw[1], yw[1]};
-      block_scalar(xwu, ywu);
-    } else {
-      block_packed(xwu, splat2(yw[1]), yw[1]);
-    }
+    block_packed(xwu, splat2(yw[1]), yw[1]);
   } else if (regular) {
-    if constexpr (SCALAR) {
+    if constexpr (RANDOM) {
       block_scalar(xw, yw);
     } else {
       block_packed(xw, (v2f){yw[0], yw[2]}, yw[1]);
@@ -740,19 +639,19 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   const float scale = 1.0f / (65535.0f * 65535.0f);
   return {first * scale, second * scale};
 }
-// RANDOM: the random-proposal form (tiled block, bias from the block) when the context keeps the tiled copy `colT`
-template <bool SCALAR, bool RANDOM = false>
+// RANDOM: the random-proposal form (bias from the block; the block from the tiled copy `colT` under DERP_RANDOM_TILED)
+template <bool RANDOM>
 __device__ __forceinline__ SsdPair compute_ssd(const LevelView& V, const PixCtx& px, const ushort4* __restrict__ col,
                                                const ushort4* __restrict__ bia, float xDstSrc, float yDstSrc,
                                                const ushort4* __restrict__ colT = nullptr) {
   SsdTexels T;
-  if constexpr (RANDOM && (DERP_RANDOM_TILED || DERP_RANDOM_BLOCK_BIAS)) {
+  if constexpr (RANDOM) {
     bool border;
-    ssd_issue_random<DERP_RANDOM_TILED != 0, DERP_RANDOM_BLOCK_BIAS != 0>(V, col, colT, bia, xDstSrc, yDstSrc, T, border);
-    return ssd_arith<SCALAR, DERP_RANDOM_BLOCK_BIAS != 0>(V, px, col, T, xDstSrc, yDstSrc, border);
+    ssd_issue_random<DERP_RANDOM_TILED != 0>(V, col, colT, bia, xDstSrc, yDstSrc, T, border);
+    return ssd_arith<true>(V, px, col, T, xDstSrc, yDstSrc, border);
   } else {
     ssd_issue(V, col, bia, xDstSrc, yDstSrc, T);
-    return ssd_arith<SCALAR>(V, px, col, T, xDstSrc, yDstSrc);
+    return ssd_arith<false>(V, px, col, T, xDstSrc, yDstSrc);
   }
 }
 
@@ -805,17 +704,14 @@ __device__ __forceinline__ unsigned behind_sources(const LevelView& V, int d, si
 // The fp64 projection state and the 4x4 texel block are never live together.
 // `cull` (wave-uniform, from behind_sources): slots of sources that no lane of the wave can see at any depth >=
 // kCullMinDepth; they are skipped without their cone test. 0 = test every source.
-// SCALAR: computeSSD's block arithmetic in plain instead of packed fp32 (ssd_arith).
-// RELOAD_RAY (ping-pong): the pixel's ray direction is read from the rayDir table at every call (pixel index `pix`)
-// instead of living in six registers across the candidate loop — where the allocator parked it in scratch (one store per
-// pixel, one load per candidate: 2.4 GB of scratch writes per level-0 launch at config 2, round 4). The opaque copy of
-// the index keeps the loads inside the loop.
+// RANDOM: the random-proposal shape of computeSSD (ssd_arith) and of `sees` (cost_sees_lean).
+// RELOAD_RAY (ping-pong, random proposals): the pixel's ray direction is read from the rayDir table at every call (pixel
+// index `pix`) instead of living in six registers across the candidate loop — where the allocator parked it in scratch
+// (one store per pixel, one load per candidate: 2.4 GB of scratch writes per level-0 launch at config 2, round 4). The
+// opaque copy of the index keeps the loads inside the loop.
 // developer build (-DDERP_PHASE_TIMERS=1|2): wave cycles (s_memtime) spent in computeCost's phases, reported through the
 // kernel's counter slots INSTEAD of the cost / pair counts: =1 -> [0] projection + taps, [1] SSD walk, [3] selection;
 // =2 -> [0] the whole kernel body, [1] everything outside computeCost. tools/phase_timers.py prints them.
-#ifndef DERP_PHASE_TIMERS
-#define DERP_PHASE_TIMERS 0
-#endif
 struct PhaseTimers {
   unsigned proj = 0, ssd = 0, select = 0, inside = 0;  // (32 bits: a wave lives < 2^32 cycles)
 };
@@ -826,16 +722,17 @@ __device__ __forceinline__ unsigned phase_clock() {
   return 0u;
 #endif
 }
-// The LEAN variant of `sees` (derp_camera.h) the cost kernels project through: ping-pong, brute force and the cost map
+// The LEAN variant of `sees` (derp_camera.h) the cost kernels project through (bit 1: the short fp64 atan2 / division
+// with the atan constants from the table in LDS): ping-pong, brute force and the cost map
 // (RANDOM = false) and random proposals (RANDOM = true; bit 2: square roots through sqrt_lean, where its three registers
 // decide between scratch and none). Ping-pong's memoised candidate 0 is random proposals' cost, so the two variants must
 // give the same bits; derp_debug_sees evaluates both through this helper.
 template <bool RANDOM>
 constexpr int cost_sees_lean() {
-  return (DERP_LEAN_PROJ != 0) * ((DERP_ATAN_LUT ? 2 : 1) + (RANDOM ? 4 : 0));
+  return 2 + (RANDOM ? 4 : 0);
 }
 
-template <bool SCALAR = false, bool RANDOM = false, bool RELOAD_RAY = false>
+template <bool RANDOM = false, bool RELOAD_RAY = false>
 __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int own, const PixCtx& px, float disparity,
                                                LdsPairs& pairs, unsigned& nPair, unsigned cull = 0, unsigned pix = 0,
                                                unsigned* slots = nullptr, PhaseTimers* tm = nullptr) {
@@ -894,15 +791,8 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
       const Cam& cs = V.camsSrc[s];
       D2 pn;
       // worldToSrcPoint (DerpUtil.cpp:56-73): Camera::sees on the normalised camera, then * (W, H)
-#ifdef DERP_ABLATE_NO_PROJ
-      const float fx = (float)pWorld.x * 0.07f + 0.013f * s, fy = (float)pWorld.y * 0.07f + 0.011f * s;
-      pn.x = 0.5 + 0.45 * (double)(fx - floorf(fx) - 0.5f);
-      pn.y = 0.5 + 0.45 * (double)(fy - floorf(fy) - 0.5f);
-      const bool vis = (s & 1) != 0;
-#else
       const bool vis = sees<cost_sees_lean<RANDOM>()>(cs, pWorld, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1],
                                                       1.0, 1.0, pn, pairs.atanLut);
-#endif
       if (__ballot(pend) != 0ull) {
         consume();
       }
@@ -949,7 +839,7 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
       const int t = __builtin_ctz(wm);
       if ((mask >> t) & 1) {
         const SsdPair e = pairs.get(t);
-        const SsdPair ssd = compute_ssd<SCALAR, RANDOM>(V, px, colBase + (size_t)t * cPlane, biaBase + (size_t)t * cPlane, e.first,
+        const SsdPair ssd = compute_ssd<RANDOM>(V, px, colBase + (size_t)t * cPlane, biaBase + (size_t)t * cPlane, e.first,
                                                         e.second, RANDOM ? colTBase + (size_t)t * tPlane : nullptr);
         pairs.set(cnt, ssd);
         ++cnt;
@@ -959,9 +849,7 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
   const unsigned tc2 = phase_clock();
   keep = max(keep, ssdCount - 2);
   GccSelect<LdsPairs> sel(pairs);
-#ifndef DERP_ABLATE_NO_SELECT
   sel.nth_element(keep, ssdCount);
-#endif
   float cost = 0;
   for (int i = 0; i < keep; ++i) {
     cost += pairs.get(i).second;
@@ -1049,7 +937,7 @@ __global__ void k_debug_atan2_ypos(const double* __restrict__ y, const double* _
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t step = (size_t)gridDim.x * blockDim.x;
 #if defined(__HIP_DEVICE_COMPILE__)  // the routine exists in the device pass only
-  // what the cost kernels evaluate (the table variant when DERP_ATAN_LUT), checked against the literal variant on
+  // what the cost kernels evaluate (the table variant), checked against the literal variant on
   // the spot: a bitwise disagreement between the two is reported as NaN, which no caller's comparison survives
   __shared__ double atanLut[kAtanLutDoubles];
   atan_lut_fill(atanLut);
@@ -1057,7 +945,7 @@ __global__ void k_debug_atan2_ypos(const double* __restrict__ y, const double* _
   for (; i < n; i += step) {
     const double a = atan2_ypos(y[i], x[i]);
     const double b = atan2_ypos_lut(y[i], x[i], atanLut);
-    out[i] = (__double_as_longlong(a) == __double_as_longlong(b)) ? (DERP_ATAN_LUT ? b : a) : __builtin_nan("");
+    out[i] = (__double_as_longlong(a) == __double_as_longlong(b)) ? b : __builtin_nan("");
   }
 #endif
 }
@@ -1087,15 +975,14 @@ __global__ void k_debug_sees(const Cam* __restrict__ cams, int src, const double
   __shared__ double atanLut[kAtanLutDoubles];
   atan_lut_fill(atanLut);
   __syncthreads();
-  const double* lut = (DERP_ATAN_LUT && DERP_LEAN_PROJ) ? atanLut : nullptr;
   const Cam& cs = cams[src];
   for (; i < n; i += step) {
     const D3 p = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     D2 a = {__builtin_nan(""), __builtin_nan("")}, b = a;
     const bool va = sees<cost_sees_lean<false>()>(cs, p, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1], 1.0, 1.0,
-                                                  a, lut);
+                                                  a, atanLut);
     const bool vb = sees<cost_sees_lean<true>()>(cs, p, cs.principal[0], cs.principal[1], cs.focal[0], cs.focal[1], 1.0, 1.0,
-                                                 b, lut);
+                                                 b, atanLut);
     double* o = out + 6 * i;
     o[0] = va ? 1.0 : 0.0;
     o[1] = a.x;
@@ -1433,7 +1320,7 @@ __global__ void k_proj_warp_inv(LevelView V, float2* __restrict__ warpInv) {
   const size_t n = (size_t)V.W * V.H;
   for (int s = 0; s < V.S; ++s) {
     // sources that are destinations of this batch: k_reproject_bias reads projWarp(ds, own) instead
-    if (s != own && (DERP_NO_WARP_IDENTITY || batch_dst_of_source(V, s) < 0)) {
+    if (s != own && batch_dst_of_source(V, s) < 0) {
       warpInv[((size_t)dl * (V.S - 1) + slot(s, own)) * n + (size_t)y * V.W + x] = warp_inv_of(V, V.camsSrc[s], inside, rig);
     }
   }
@@ -1476,7 +1363,7 @@ __global__ void __launch_bounds__(256)
   // function, see batch_dst_of_source; that table carries a 1-texel ring), the stored projWarpInv otherwise
   const float2* map = warpInv + (size_t)tab * n;
   int mapPitch = V.W;
-  const int ds = DERP_NO_WARP_IDENTITY ? -1 : batch_dst_of_source(V, s);
+  const int ds = batch_dst_of_source(V, s);
   if (ds >= 0) {
     mapPitch = V.W + 2 * kPadW;
     map = V.projWarp + ((size_t)ds * (V.S - 1) + slot(own, s)) * warp_plane(V) + (size_t)kPadW * mapPitch + kPadW;
@@ -1553,9 +1440,8 @@ __device__ __forceinline__ float probe_disparity(int i, float minD, float maxD) 
   return (float)(fraction * (double)minD + (1 - fraction) * (double)maxD);
 }
 
-__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
+__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
     k_brute_costs(LevelView V, float* __restrict__ costs, float* __restrict__ confs, int tilesX, int tilesPerDst) {
-  extern __shared__ SsdPair ldsPairs[];
   const int i = blockIdx.y;   // disparity index
   const int dl = blockIdx.z;
   const int d = V.dst0 + dl;
@@ -1565,18 +1451,8 @@ __global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
   const int lane = threadIdx.x & 63;
   const int sx = (int)(blockIdx.x % (unsigned)tilesX), sy = (int)(blockIdx.x / (unsigned)tilesX);
   const int x = 1 + sx * 8 + (lane & 7), y = 1 + sy * 8 + (lane >> 3);
-  // the wave's 10x10 window of destination colours (PatchWin): filled by all 64 lanes before anything diverges
-  __shared__ PatchWin patchWin[DERP_COST_BLOCK / 64];
-  PatchWin* win = &patchWin[threadIdx.x >> 6];
-  patch_window_fill(V, V.dst2src[d], x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
-#if DERP_ATAN_LUT && DERP_LEAN_PROJ && defined(__HIP_DEVICE_COMPILE__)
-  __shared__ double atanLut[kAtanLutDoubles];
-  atan_lut_fill(atanLut);
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
-#else
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
-#endif
-  __syncthreads();
+  PatchWin* win;
+  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
   unsigned nCost = 0, nPair = 0;
   if (x <= iw && y <= ih) {
     const int own = V.dst2src[d];
@@ -1589,7 +1465,7 @@ __global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
     if (fov && fg && closer) {
       PixCtx px;
       load_pixctx(V, d, own, x, y, win, px);
-      r = compute_cost<DERP_COST_SSD_SCALAR != 0>(V, dl, own, px, disparity, pairs, nPair);
+      r = compute_cost(V, dl, own, px, disparity, pairs, nPair);
       ++nCost;
     }
     const size_t o = ((size_t)dl * kNumDepths + i) * n + idx;
@@ -1713,23 +1589,12 @@ __global__ void __launch_bounds__(256) k_row_rank(LevelView V, int* __restrict__
 
 // (the body of k_random_proposals / k_random_proposals_w3: the same code under two register budgets, see below)
 __device__ __forceinline__ void random_proposals_body(const LevelView& V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
-  extern __shared__ SsdPair ldsPairs[];
   const int dl = blockIdx.y;
   const int d = V.dst0 + dl;
   int x, y;
-  tile_pixel(DERP_RANDOM_SWIZZLE ? xcd_swizzle(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0) : (int)blockIdx.x, tilesX, x, y);
-  // the wave's 10x10 window of destination colours (PatchWin): filled by all 64 lanes before anything diverges
-  __shared__ PatchWin patchWin[DERP_COST_BLOCK / 64];
-  PatchWin* win = &patchWin[threadIdx.x >> 6];
-  patch_window_fill(V, V.dst2src[d], x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
-#if DERP_ATAN_LUT && DERP_LEAN_PROJ && defined(__HIP_DEVICE_COMPILE__)
-  __shared__ double atanLut[kAtanLutDoubles];
-  atan_lut_fill(atanLut);
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
-#else
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
-#endif
-  __syncthreads();
+  tile_pixel(xcd_swizzle(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0), tilesX, x, y);
+  PatchWin* win;
+  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
   unsigned nCost = 0, nPair = 0, nSlots = 0, nSlotsFirst = 0;
   PhaseTimers tm;
   const unsigned tk0 = phase_clock();
@@ -1744,8 +1609,8 @@ __device__ __forceinline__ void random_proposals_body(const LevelView& V, const 
         disp[idx] = (V.bgDisp + (size_t)d * n)[idx];
       } else if (random_gate(V, d, own, idx)) {
         PixCtx px;
-        load_pixctx<!DERP_RANDOM_RELOAD_RAY>(V, d, own, x, y, win, px);
-        const unsigned cull = DERP_SOURCE_CULL ? behind_sources(V, d, idx) : 0u;
+        load_pixctx<false>(V, d, own, x, y, win, px);
+        const unsigned cull = behind_sources(V, d, idx);
         // What the proposal loop carries per lane: the pixel index, the current disparity / cost / confidence / pair count,
         // the acceptance threshold, the amplitude, the engine state, the pair counter; the lower bound of the range is
         // read again per proposal.
@@ -1768,7 +1633,7 @@ __device__ __forceinline__ void random_proposals_body(const LevelView& V, const 
             propDisp = minstd_uniform(state, lo, hi);
           }
           unsigned np = 0;
-          const float2 pr = compute_cost<DERP_RANDOM_SSD_SCALAR != 0, true, DERP_RANDOM_RELOAD_RAY != 0>(V, dl, own, px, propDisp, pairs, np, cull, pi, i < 0 ? &nSlotsFirst : &nSlots, &tm);
+          const float2 pr = compute_cost<true, true>(V, dl, own, px, propDisp, pairs, np, cull, pi, i < 0 ? &nSlotsFirst : &nSlots, &tm);
           nPair += np;
           bool take;
           if (i < 0) {
@@ -1821,11 +1686,11 @@ __device__ __forceinline__ void random_proposals_body(const LevelView& V, const 
 // pair slots fill the LDS first (24 cameras: twelve blocks = three waves) and the 128-register build would pay its spills
 // and tighter schedule for nothing: the _w3 kernels keep the 168 registers of three waves (config 4, same box: 261 -> 271
 // Mpix/s, profiles/r06_kernel_variants.txt run 9). The launcher picks by camera count (cost_four_waves, derp_capi.hip).
-__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_RANDOM_MIN_WAVES)
+__global__ void __launch_bounds__(kCostBlock, DERP_RANDOM_MIN_WAVES)
     k_random_proposals(LevelView V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
   random_proposals_body(V, rank, tilesX, tilesPerDst);
 }
-__global__ void __launch_bounds__(DERP_COST_BLOCK, 3)
+__global__ void __launch_bounds__(kCostBlock, 3)
     k_random_proposals_w3(LevelView V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
   random_proposals_body(V, rank, tilesX, tilesPerDst);
 }
@@ -1875,8 +1740,8 @@ __device__ __forceinline__ void ping_pong_candidates_loop(const LevelView& V, co
       outDisp = V.bgDisp[(size_t)d * n + idx];
     } else if (!(V.srcVar[(size_t)own * n + idx] < V.varNoiseFloor)) {
       PixCtx px;
-      load_pixctx<!DERP_PP_RELOAD_RAY>(V, d, own, x, y, win, px);
-      const unsigned cull = DERP_SOURCE_CULL ? behind_sources(V, d, idx) : 0u;
+      load_pixctx<false>(V, d, own, x, y, win, px);
+      const unsigned cull = behind_sources(V, d, idx);
       float bestCost = __builtin_inff();
       float bestDisp = outDisp;
       // what the candidate loop carries per lane: the pixel (x | y << 16), the best candidate so far, the counters.
@@ -1908,7 +1773,7 @@ __device__ __forceinline__ void ping_pong_candidates_loop(const LevelView& V, co
 #ifdef DERP_COUNT_PP_FILL
               fillSlots += pp_fill_entry();
 #endif
-              r = compute_cost<DERP_COST_SSD_SCALAR != 0, false, DERP_PP_RELOAD_RAY != 0>(V, dl, own, px, cand, pairs, np, cull, pidx, nullptr, &tm);
+              r = compute_cost<false, true>(V, dl, own, px, cand, pairs, np, cull, pidx, nullptr, &tm);
               counts += np;
             }
             counts += 1u << 16;
@@ -1986,15 +1851,13 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
   }
   // the cull mask of the evaluating lanes (behind_sources' ballot, with the other lanes made neutral)
   unsigned cull = 0;
-  if (DERP_SOURCE_CULL) {
-    const unsigned m = eval ? V.behind[(size_t)d * n + idx] : ~0u;
-    for (int t = 0; t < V.S - 1; ++t) {
-      if (__ballot(!((m >> t) & 1u)) == 0ull) {
-        cull |= 1u << t;
-      }
+  const unsigned behind = eval ? V.behind[(size_t)d * n + idx] : ~0u;
+  for (int t = 0; t < V.S - 1; ++t) {
+    if (__ballot(!((behind >> t) & 1u)) == 0ull) {
+      cull |= 1u << t;
     }
-    cull = __builtin_amdgcn_readfirstlane(cull);
   }
+  cull = __builtin_amdgcn_readfirstlane(cull);
   // 2. the task list: inclusive prefix sum of the per-pixel task counts
   int incl = __popc(cmask);
   for (int off = 1; off < 64; off <<= 1) {
@@ -2043,10 +1906,10 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
       const int yy = min(max(oy + (int)((kCandPackY >> (3 * k)) & 7u) - 2, 0), V.H - 1);
       const float cand = disp[(unsigned)yy * (unsigned)V.W + (unsigned)xx];
       PixCtx px;
-      load_pixctx<!DERP_PP_RELOAD_RAY>(V, d, own, ox, oy, win, px, o);
+      load_pixctx<false>(V, d, own, ox, oy, win, px, o);
       LdsPairs lp{wavePairs + ln, pairs.stride, pairs.atanLut};
       unsigned np = 0;
-      const float2 r = compute_cost<DERP_COST_SSD_SCALAR != 0, false, DERP_PP_RELOAD_RAY != 0>(V, dl, own, px, cand, lp, np, cull, pidx, nullptr, &tm);
+      const float2 r = compute_cost<false, true>(V, dl, own, px, cand, lp, np, cull, pidx, nullptr, &tm);
       counts += np + (1u << 16);
       int sl = lane;
       asm("" : "+v"(sl) : "v"(r.x));
@@ -2074,23 +1937,12 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
 template <bool COMPACT>
 __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                                                float* __restrict__ costRes, int tilesX, int useMemo) {
-  extern __shared__ SsdPair ldsPairs[];
   const int dl = blockIdx.y;
   const int d = V.dst0 + dl;
   int x, y;
   tile_pixel(xcd_swizzle(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0), tilesX, x, y);
-  // the wave's 10x10 window of destination colours (PatchWin): filled by all 64 lanes before anything diverges
-  __shared__ PatchWin patchWin[DERP_COST_BLOCK / 64];
-  PatchWin* win = &patchWin[threadIdx.x >> 6];
-  patch_window_fill(V, V.dst2src[d], x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
-#if DERP_ATAN_LUT && DERP_LEAN_PROJ && defined(__HIP_DEVICE_COMPILE__)
-  __shared__ double atanLut[kAtanLutDoubles];
-  atan_lut_fill(atanLut);
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
-#else
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
-#endif
-  __syncthreads();
+  PatchWin* win;
+  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
   // per-lane counters in one register: pairs (bits 0..15: <= 10 * 31), cost evaluations (16..23: <= 10), memoised (24..)
   unsigned counts = 0, fillSlots = 0;
   PhaseTimers tm;
@@ -2135,22 +1987,22 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
 
 // Two register budgets (see k_random_proposals_w3) x two candidate loops: the compacted one, and the one-pixel-per-lane
 // loop it replaced (DERP_PP_COMPACT=0, developer A/B). The launcher picks (run_ping_pong, derp_capi.hip).
-__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
+__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
     k_ping_pong(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                 float* __restrict__ costRes, int tilesX, int useMemo) {
   ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
 }
-__global__ void __launch_bounds__(DERP_COST_BLOCK, 3)  // more than 16 cameras: see k_random_proposals_w3
+__global__ void __launch_bounds__(kCostBlock, 3)  // more than 16 cameras: see k_random_proposals_w3
     k_ping_pong_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                    float* __restrict__ costRes, int tilesX, int useMemo) {
   ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
 }
-__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
+__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
     k_ping_pong_loop(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                      float* __restrict__ costRes, int tilesX, int useMemo) {
   ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
 }
-__global__ void __launch_bounds__(DERP_COST_BLOCK, 3)
+__global__ void __launch_bounds__(kCostBlock, 3)
     k_ping_pong_loop_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
                         float* __restrict__ costRes, int tilesX, int useMemo) {
   ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
@@ -2270,31 +2122,20 @@ __global__ void k_layer_disparities(const float* __restrict__ fg, const float* _
 }
 
 // cost map of a caller-supplied disparity image (test hook over compute_cost)
-__global__ void __launch_bounds__(DERP_COST_BLOCK, DERP_COST_MIN_WAVES)
+__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
     k_cost_map(LevelView V, int d, const float* __restrict__ dispIn, float* __restrict__ costOut,
                float* __restrict__ confOut, int tilesX) {
-  extern __shared__ SsdPair ldsPairs[];
   const int dl = d - V.dst0;
   int x, y;
   tile_pixel(blockIdx.x, tilesX, x, y);
-  // the wave's 10x10 window of destination colours (PatchWin): filled by all 64 lanes before anything diverges
-  __shared__ PatchWin patchWin[DERP_COST_BLOCK / 64];
-  PatchWin* win = &patchWin[threadIdx.x >> 6];
-  patch_window_fill(V, V.dst2src[d], x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
-#if DERP_ATAN_LUT && DERP_LEAN_PROJ && defined(__HIP_DEVICE_COMPILE__)
-  __shared__ double atanLut[kAtanLutDoubles];
-  atan_lut_fill(atanLut);
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
-#else
-  LdsPairs pairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
-#endif
-  __syncthreads();
+  PatchWin* win;
+  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
   unsigned nCost = 0, nPair = 0;
   if (x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1) {
     const int own = V.dst2src[d];
     PixCtx px;
     load_pixctx(V, d, own, x, y, win, px);
-    const float2 r = compute_cost<DERP_COST_SSD_SCALAR != 0>(V, dl, own, px, dispIn[(size_t)y * V.W + x], pairs, nPair);
+    const float2 r = compute_cost(V, dl, own, px, dispIn[(size_t)y * V.W + x], pairs, nPair);
     ++nCost;
     costOut[(size_t)y * V.W + x] = r.x;
     confOut[(size_t)y * V.W + x] = r.y;

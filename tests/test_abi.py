@@ -79,7 +79,7 @@ def test_restated_libstdcxx_algorithms(built):
 
 def test_block_bias_rounding_identity():
     """k_random_proposals sums the 3x3 colour-bias boxes from the 4x4 texel block in fp32 and rounds with
-    trunc((s + 4) * fl(1/9)) (derp_kernels.h, DERP_RANDOM_BLOCK_BIAS); k_reproject_bias, like cv::blur on CV_16UC3
+    trunc((s + 4) * fl(1/9)) (derp_kernels.h, ssd_arith<RANDOM = true>); k_reproject_bias, like cv::blur on CV_16UC3
     (DerpUtil.cpp:208-210), rounds the integer sum with (s + 4) / 9. The two agree for EVERY possible sum of nine
     16-bit texels, and every such sum (+ 4) is exact in fp32."""
     import numpy as np

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer A/B: build facebook360_dep_amd/libderp_var_<name>.so for every "<name>:<extra hipcc flags>" argument
 # (tools/variants.sh then runs parity + bench on each through DERP_LIB). Runs here: hipcc cross-compiles gfx950.
-#   tools/build_variants.sh "base:-DDERP_ATAN_LUT=0" "sc:-DDERP_SSD_SCALAR=1 -fno-slp-vectorize"
+#   tools/build_variants.sh "base:" "w3:-DDERP_COST_MIN_WAVES=3 -DDERP_RANDOM_MIN_WAVES=3" "tiled:-DDERP_RANDOM_TILED=1"
 cd "$(dirname "$0")/.."
 rm -f facebook360_dep_amd/libderp_var_*.so
 for spec in "$@"; do
