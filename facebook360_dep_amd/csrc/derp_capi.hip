@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -46,18 +47,36 @@ const char* kStageNames[ST_COUNT] = {"fov_mask",  "variance",    "own_bias",    
                                      "temporal",  "lanes_wall"};
 constexpr int kMaxLevels = 24;
 
+// A device allocation and its owner: move-only, freed when the owner dies
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+    o.p = nullptr;
+    o.bytes = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      bytes = o.bytes;
+      o.p = nullptr;
+      o.bytes = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() {
+    release();
+  }
+  // grow-only; the contents are lost on growth; non-zero (and an empty buffer) when the allocation fails
   int ensure(size_t n) {
     if (n <= bytes) {
       return 0;
     }
-    if (p) {
-      (void)hipFree(p);
-      p = nullptr;
-      bytes = 0;
-    }
+    release();
     if (hipMalloc(&p, n) != hipSuccess) {
       p = nullptr;
       return 1;
@@ -92,6 +111,44 @@ struct AreaTabDev {  // computeResizeAreaTab of one axis, resident in HBM
   int iscale = 0;
 };
 
+// Everything processLevel writes per frame. The context has one and every work lane has one; the rig-only tables of a
+// level (projWarp, projWarpInv, rayDir, behind, resampling tables) are shared by the lanes and stay on the context.
+struct WorkSet {
+  DevBuf srcVar, ownBias, fovMask, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
+  DevBuf tileSeen;    // k_reproject_bias: per (table, tile) whether any map position is valid
+  DevBuf projColor, projBias;
+  DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)
+  DevBuf bruteCost, bruteConf, lanczosTmp, staging, stagingB;
+  int colorTablesCleanLevel = -1;  // level whose colour / bias tables were written in full since its warps were built
+};
+
+// HBM-resident pyramid of one frame, per level: colour, fg masks, background disparity, result
+struct FramePyramid {
+  std::vector<DevBuf> color, fg, bg, disp;
+  std::vector<char> haveBg, haveDisp;
+};
+
+struct WorkLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  WorkSet w;
+};
+
+// derp_render_*: SimpleMeshRenderer's scene (derp_render.h)
+struct SmrCam {
+  int dw = 0, dh = 0, tw = 0, th = 0;  // disparity (mesh) and colour texture sizes
+  CanopyMips Mc, Md;                   // mip geometry of the colour texture and of the disparity-colour texture
+  DevBuf vert, eyeVert, texColor, texDisp;
+  float eyeIpd = 0.0f;  // ipdm eyeVert was computed for (0: none yet)
+};
+struct SmrState {
+  std::vector<SmrCam> cams;
+  bool haveColor = false;
+  bool dispValid = false;
+  float dispPos[3] = {0, 0, 0};  // position the disparity colours were computed for
+  DevBuf zbuf, acc, big, nBig, cube, img, img2, tabs, back, equi, fetch, staging;
+};
+
 }  // namespace
 
 struct derp_ctx {
@@ -100,7 +157,7 @@ struct derp_ctx {
   hipStream_t copyStream = nullptr;  // input uploads of a frame that is not being computed (sequence driver), with
   DevBuf copyStaging;                // their own staging buffer: they overlap the compute of the frame before
   DevBuf cnVert, cnRgba, cnZ, cnAcc, cnOut, cnBig, cnNBig;  // derp_canopy_cubemap's buffers, kept between calls
-  struct SmrState* smr = nullptr;                           // derp_render_*'s scene (derp_render_upload)
+  std::unique_ptr<SmrState> smr;                            // derp_render_*'s scene (derp_render_upload)
   std::string err;
   derp_options opt;
   int S = 0, D = 0;
@@ -110,34 +167,28 @@ struct derp_ctx {
 
   int numLevels = 0, widthFull = 0, heightFull = 0;
   std::vector<int> LW, LH;
-  // HBM-resident pyramid of the SELECTED frame slot; the other slots' pyramids are parked in `parked`
-  // (derp_set_frame_slots / derp_select_frame: several frames of one sequence resident on this GPU)
-  std::vector<DevBuf> pyrColor, pyrFg, pyrBg, pyrDisp;
-  std::vector<char> haveBg, haveDisp;
-  struct FrameSlot {
-    std::vector<DevBuf> pyrColor, pyrFg, pyrBg, pyrDisp;
-    std::vector<char> haveBg, haveDisp;
-  };
-  std::vector<FrameSlot> parked;  // parked[curSlot] is empty while that slot is selected
+  // one pyramid per frame slot (derp_set_frame_slots / derp_select_frame: several frames of one sequence resident on
+  // this GPU); the level loop works on the selected one
+  std::vector<FramePyramid> frames;
   int curSlot = 0;
+  FramePyramid& frame() {
+    return frames[curSlot];
+  }
   int xcdRotate = 1;
 
   // working level
   int cur = -1;
   int DB = 0;  // dst batch that fits the table budget
-  DevBuf srcVar, ownBias, fovMask, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
+  WorkSet w;             // the per-frame working set in use: the context's own, or a lane's while its frame runs
   DevBuf temporalCarry;  // accumulators of a temporal window longer than one launch holds
-  DevBuf tileSeen;       // k_reproject_bias: per (table, tile) whether any map position is valid
-  int colorTablesCleanLevel = -1;  // level whose colour / bias tables were written in full since its warps were built
-  DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)
-  DevBuf projWarp, projColor, projBias, projWarpInv, bruteCost, bruteConf, lanczosTmp, staging, stagingB;
+  DevBuf projWarp, projWarpInv;
   DevBuf rayDir, behind;  // per destination pixel: ray direction [3][D][n] f64, sources facing away [D][n] (k_pixel_rays)
   int warpCachedLevel = -1;
   bool randomRanThisLevel = false;  // cost / confidence hold random-proposal results for this level
   bool tablesValid = false;
   DevBuf counters;  // [ST_COUNT][kMaxLevels][4] u64
-  std::map<std::pair<int, int>, LanczosTab*> lanczos;
-  std::map<std::pair<int, int>, AreaTabDev*> areaTabs;
+  std::map<std::pair<int, int>, LanczosTab> lanczos;  // (map nodes keep their addresses: get_lanczos / get_area_tab
+  std::map<std::pair<int, int>, AreaTabDev> areaTabs;  // hand out pointers into them)
   DevBuf fullFrame;
   DevBuf devMask;  // derp_dev_mask result (not a working buffer)
   DevBuf rephotoColor, rephotoDisp;  // derp_rephotograph_upload: S planes of BGR u16 / f32 disparity
@@ -149,17 +200,11 @@ struct derp_ctx {
   // same coarse level (derp_seq_level_compute). The frames of a level are independent, and at the coarse levels one
   // frame's kernels fill a fraction of the chip (level 6 of the 16-camera rig: 784 waves for 4096 wave slots) and are
   // bound by their own serial latency — on lanes the frames' kernels overlap. A lane holds everything processLevel writes
-  // per frame; the rig-only tables of the level (projWarp, projWarpInv, rayDir, behind, resampling tables) stay shared.
-  struct WorkLane {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    DevBuf srcVar, ownBias, fovMask, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask,
-        pairCount, tileSeen, projColor, projBias, projColorT, bruteCost, bruteConf, lanczosTmp, staging, stagingB;
-    int colorTablesCleanLevel = -1;
-  };
-  std::vector<WorkLane*> lanes;
+  // per frame (a WorkSet); the rig-only tables of the level (projWarp, projWarpInv, rayDir, behind, resampling tables) stay
+  // shared.
+  std::vector<std::unique_ptr<WorkLane>> lanes;
   hipEvent_t laneReady = nullptr;  // recorded on the main stream behind what the lanes' frames depend on
-  int activeLane = -1;             // the lane whose members are swapped in (-1: the context's own)
+  int activeLane = -1;             // the lane whose work set is swapped in (-1: the context's own)
 
   bool profiling = false;
   bool noMemo = false;  // DERP_NO_MEMO (developer switch), read once in derp_create
@@ -282,23 +327,23 @@ LevelView make_view(derp_ctx* c, int stage, int dst0, int nd) {
   V.camsSrc = c->camsSrc.as<Cam>();
   V.camsDst = c->camsDst.as<Cam>();
   V.dst2src = c->dst2src.as<int>();
-  V.srcColor = c->pyrColor[L].as<ushort4>();
-  V.ownBias = c->ownBias.as<ushort4>();
-  V.srcVar = c->srcVar.as<float>();
-  V.srcFg = c->pyrFg[L].as<uint8_t>();
+  V.srcColor = c->frame().color[L].as<ushort4>();
+  V.ownBias = c->w.ownBias.as<ushort4>();
+  V.srcVar = c->w.srcVar.as<float>();
+  V.srcFg = c->frame().fg[L].as<uint8_t>();
   V.rayDir = c->rayDir.as<double>();
   V.behind = c->behind.as<unsigned>();
   V.rayStride = (size_t)c->D * V.W * V.H;
   V.projWarp = c->projWarp.as<float2>();
-  V.projColor = c->projColor.as<ushort4>();
-  V.projBias = c->projBias.as<ushort4>();
-  V.projColorT = c->projColorT.as<ushort4>();
-  V.disparity = c->disparity.as<float>();
-  V.cost = c->cost.as<float>();
-  V.confidence = c->confidence.as<float>();
-  V.bgDisp = c->pyrBg[L].as<float>();
-  V.fovMask = c->fovMask.as<uint8_t>();
-  V.pairCount = c->pairCount.as<uint8_t>();
+  V.projColor = c->w.projColor.as<ushort4>();
+  V.projBias = c->w.projBias.as<ushort4>();
+  V.projColorT = c->w.projColorT.as<ushort4>();
+  V.disparity = c->w.disparity.as<float>();
+  V.cost = c->w.cost.as<float>();
+  V.confidence = c->w.confidence.as<float>();
+  V.bgDisp = c->frame().bg[L].as<float>();
+  V.fovMask = c->w.fovMask.as<uint8_t>();
+  V.pairCount = c->w.pairCount.as<uint8_t>();
   V.counters = counter_slot(c, stage, L);
   return V;
 }
@@ -346,7 +391,7 @@ int get_lanczos(derp_ctx* c, int ssize, int dsize, LanczosTab** out) {
   auto key = std::make_pair(ssize, dsize);
   auto it = c->lanczos.find(key);
   if (it != c->lanczos.end()) {
-    *out = it->second;
+    *out = &it->second;
     return 0;
   }
   std::vector<int> ofs(dsize);
@@ -360,14 +405,13 @@ int get_lanczos(derp_ctx* c, int ssize, int dsize, LanczosTab** out) {
     ofs[d] = s;
     lanczos_coeffs(f, &coef[(size_t)d * 8]);
   }
-  LanczosTab* t = new LanczosTab;
-  ALLOC(c, t->ofs, ofs.size() * sizeof(int));
-  ALLOC(c, t->coef, coef.size() * sizeof(float));
-  HIPCHK(c, hipMemcpyAsync(t->ofs.p, ofs.data(), ofs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(t->coef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  LanczosTab t;
+  ALLOC(c, t.ofs, ofs.size() * sizeof(int));
+  ALLOC(c, t.coef, coef.size() * sizeof(float));
+  HIPCHK(c, hipMemcpyAsync(t.ofs.p, ofs.data(), ofs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(t.coef.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // host vectors go out of scope
-  c->lanczos[key] = t;
-  *out = t;
+  *out = &(c->lanczos[key] = std::move(t));
   return 0;
 }
 
@@ -379,16 +423,16 @@ int get_area_tab(derp_ctx* c, int ssize, int dsize, AreaTabDev** out, bool force
   auto key = std::make_pair(forceTable ? -ssize : ssize, dsize);
   auto it = c->areaTabs.find(key);
   if (it != c->areaTabs.end()) {
-    *out = it->second;
+    *out = &it->second;
     return 0;
   }
-  AreaTabDev* t = new AreaTabDev;
+  AreaTabDev t;
   const double scale = (double)ssize / dsize;
   const int iscale = (int)std::nearbyint(scale);
   std::vector<int> start(dsize + 1, 0), si;
   std::vector<float> alpha;
   if (!forceTable && iscale >= 1 && std::abs(scale - iscale) < 2.220446049250313e-16) {
-    t->iscale = iscale;
+    t.iscale = iscale;
   } else {
     for (int dx = 0; dx < dsize; ++dx) {
       start[dx] = (int)si.size();
@@ -416,14 +460,13 @@ int get_area_tab(derp_ctx* c, int ssize, int dsize, AreaTabDev** out, bool force
     si.push_back(0);
     alpha.push_back(0.f);
   }
-  ALLOC(c, t->start, start.size() * sizeof(int));
-  ALLOC(c, t->si, si.size() * sizeof(int));
-  ALLOC(c, t->alpha, alpha.size() * sizeof(float));
-  HIPCHK(c, hipMemcpy(t->start.p, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(t->si.p, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(t->alpha.p, alpha.data(), alpha.size() * sizeof(float), hipMemcpyHostToDevice));
-  c->areaTabs[key] = t;
-  *out = t;
+  ALLOC(c, t.start, start.size() * sizeof(int));
+  ALLOC(c, t.si, si.size() * sizeof(int));
+  ALLOC(c, t.alpha, alpha.size() * sizeof(float));
+  HIPCHK(c, hipMemcpy(t.start.p, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(t.si.p, si.data(), si.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(t.alpha.p, alpha.data(), alpha.size() * sizeof(float), hipMemcpyHostToDevice));
+  *out = &(c->areaTabs[key] = std::move(t));
   return 0;
 }
 
@@ -512,11 +555,11 @@ int upsample_lanczos_dev(derp_ctx* c, const float* in, int sw, int sh, float* ou
   TRY(get_lanczos(c, sw, dw, &tx));
   TRY(get_lanczos(c, sh, dh, &ty));
   const size_t tmpStride = (size_t)dw * sh;
-  ALLOC(c, c->lanczosTmp, tmpStride * planes * sizeof(float));
+  ALLOC(c, c->w.lanczosTmp, tmpStride * planes * sizeof(float));
   hipLaunchKernelGGL(k_lanczos_h, grid2d(dw, sh, planes, kBlk2d), kBlk2d, 0, c->stream, in, sw, sh, dw,
-                     tx->ofs.as<int>(), tx->coef.as<float>(), c->lanczosTmp.as<float>(), inStride, tmpStride);
+                     tx->ofs.as<int>(), tx->coef.as<float>(), c->w.lanczosTmp.as<float>(), inStride, tmpStride);
   KCHECK(c);
-  hipLaunchKernelGGL(k_lanczos_v, grid2d(dw, dh, planes, kBlk2d), kBlk2d, 0, c->stream, c->lanczosTmp.as<float>(), sh,
+  hipLaunchKernelGGL(k_lanczos_v, grid2d(dw, dh, planes, kBlk2d), kBlk2d, 0, c->stream, c->w.lanczosTmp.as<float>(), sh,
                      dw, dh, ty->ofs.as<int>(), ty->coef.as<float>(), out, tmpStride, outStride);
   KCHECK(c);
   return 0;
@@ -529,11 +572,11 @@ int upsample_masked_dev(derp_ctx* c, const float* in, const uint8_t* mask, int s
   const float scale = float(dw) / float(sw);
   const int radius = (int)(scale * scale + 1);
   TRY(ensure_spiral(c, radius));
-  ALLOC(c, c->lanczosTmp, (size_t)dw * dh * planes * sizeof(float));
+  ALLOC(c, c->w.lanczosTmp, (size_t)dw * dh * planes * sizeof(float));
   hipLaunchKernelGGL(k_upsample_nearest_masked, grid2d(dw, dh, planes, kBlk2d), kBlk2d, 0, c->stream, in, mask, sw, sh,
-                     maskUp, dw, dh, c->lanczosTmp.as<float>());
+                     maskUp, dw, dh, c->w.lanczosTmp.as<float>());
   KCHECK(c);
-  hipLaunchKernelGGL(k_spiral_fill, grid2d(dw, dh, planes, kBlk2d), kBlk2d, 0, c->stream, c->lanczosTmp.as<float>(), bgUp,
+  hipLaunchKernelGGL(k_spiral_fill, grid2d(dw, dh, planes, kBlk2d), kBlk2d, 0, c->stream, c->w.lanczosTmp.as<float>(), bgUp,
                      maskUp, dw, dh, c->spiral.as<int2>(), c->spiralN, out);
   KCHECK(c);
   return 0;
@@ -566,10 +609,10 @@ int compute_fov_and_masks(derp_ctx* c, int level) {
   {
     Span sp(c, ST_FOV, level);
     hipLaunchKernelGGL(k_fov_mask, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>(), W, H,
-                       c->fovMask.as<uint8_t>());
+                       c->w.fovMask.as<uint8_t>());
     KCHECK(c);
-    hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), c->D), dim3(256), 0, c->stream, c->fovMask.as<uint8_t>(),
-                       c->pyrFg[level].as<uint8_t>(), c->dst2src.as<int>(), 0, n, c->maskAnd.as<uint8_t>());
+    hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), c->D), dim3(256), 0, c->stream, c->w.fovMask.as<uint8_t>(),
+                       c->frame().fg[level].as<uint8_t>(), c->dst2src.as<int>(), 0, n, c->w.maskAnd.as<uint8_t>());
     KCHECK(c);
   }
   return 0;
@@ -591,7 +634,7 @@ int build_warp(derp_ctx* c, int dst0, int nd) {
   hipLaunchKernelGGL(k_pixel_rays, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->rayDir.as<double>(),
                      c->behind.as<unsigned>());
   KCHECK(c);
-  c->colorTablesCleanLevel = -1;  // new warps (another level, batch or rig state): the colour tables must be rewritten in full
+  c->w.colorTablesCleanLevel = -1;  // new warps (another level, batch or rig state): the colour tables must be rewritten in full
   // ... and the inverse warps reprojectColors reads (projWarpInv, PyramidLevel.h:46-51) — those that are not a
   // projWarp table of this batch already (all of them are when every source is a destination of the batch)
   if (batch_needs_inverse_warps(c, dst0, nd)) {
@@ -607,15 +650,15 @@ int build_color_tables(derp_ctx* c, int dst0, int nd) {
   // colours and their 3x3 biases in one pass (the bias stage's time is inside ST_REPROJECT now)
   Span sp(c, ST_REPROJECT, L);
   const dim3 grid((V.W + kRbTile - 1) / kRbTile, (V.H + kRbTile - 1) / kRbTile, nd * (c->S - 1));
-  ALLOC(c, c->tileSeen, (size_t)grid.x * grid.y * grid.z);
+  ALLOC(c, c->w.tileSeen, (size_t)grid.x * grid.y * grid.z);
   // a frame that finds the tables of this level as an earlier frame left them (same warps: a sequence running the
   // level frame after frame) skips the tiles no source pixel maps into — they still hold their zeros
-  const int skipBlank = c->colorTablesCleanLevel == L && nd == c->D && !c->noBlankSkip;
+  const int skipBlank = c->w.colorTablesCleanLevel == L && nd == c->D && !c->noBlankSkip;
   hipLaunchKernelGGL(k_reproject_bias, grid, dim3(256), 0, c->stream, V, c->projWarpInv.as<float2>(),
-                     c->projColor.as<ushort4>(), c->projBias.as<ushort4>(), c->projColorT.as<ushort4>(),
-                     c->tileSeen.as<uint8_t>(), skipBlank);
+                     c->w.projColor.as<ushort4>(), c->w.projBias.as<ushort4>(), c->w.projColorT.as<ushort4>(),
+                     c->w.tileSeen.as<uint8_t>(), skipBlank);
   KCHECK(c);
-  c->colorTablesCleanLevel = nd == c->D ? L : -1;
+  c->w.colorTablesCleanLevel = nd == c->D ? L : -1;
   return 0;
 }
 
@@ -658,17 +701,17 @@ int run_brute_force(derp_ctx* c, int dst0, int nd) {
   Span sp(c, ST_BRUTE, L);
   LevelView V = make_view(c, ST_BRUTE, dst0, nd);
   const size_t n = (size_t)V.W * V.H;
-  ALLOC(c, c->bruteCost, (size_t)nd * kNumDepths * n * sizeof(float));
-  ALLOC(c, c->bruteConf, (size_t)nd * kNumDepths * n * sizeof(float));
+  ALLOC(c, c->w.bruteCost, (size_t)nd * kNumDepths * n * sizeof(float));
+  ALLOC(c, c->w.bruteConf, (size_t)nd * kNumDepths * n * sizeof(float));
   // 8 x 8 pixel strips over the interior (W - 2) x (H - 2) pixels, one wave each
   const int tilesX = std::max(1, (V.W - 2 + 7) / 8), tilesY = std::max(1, (V.H - 2 + 7) / 8);
   const int tiles = tilesX * tilesY;
   const size_t lds = kCostLdsPerSrc * (size_t)(c->S);
   hipLaunchKernelGGL(k_brute_costs, dim3(tiles, kNumDepths, nd), dim3(kCostBlock), lds, c->stream, V,
-                     c->bruteCost.as<float>(), c->bruteConf.as<float>(), tilesX, tiles);
+                     c->w.bruteCost.as<float>(), c->w.bruteConf.as<float>(), tilesX, tiles);
   KCHECK(c);
-  hipLaunchKernelGGL(k_brute_select, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->bruteCost.as<float>(),
-                     c->bruteConf.as<float>());
+  hipLaunchKernelGGL(k_brute_select, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->w.bruteCost.as<float>(),
+                     c->w.bruteConf.as<float>());
   KCHECK(c);
   hipLaunchKernelGGL(k_brute_margin, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V);
   KCHECK(c);
@@ -684,14 +727,14 @@ int run_random_proposals(derp_ctx* c, int dst0, int nd) {
   c->randomRanThisLevel = true;
   LevelView V = make_view(c, ST_RANDOM, dst0, nd);
   if (V.H > 2 && V.W > 2) {
-    hipLaunchKernelGGL(k_row_rank, dim3(V.H - 2, nd), dim3(256), 0, c->stream, V, c->rank.as<int>());
+    hipLaunchKernelGGL(k_row_rank, dim3(V.H - 2, nd), dim3(256), 0, c->stream, V, c->w.rank.as<int>());
     KCHECK(c);
   }
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->randomWaves, c->ldsPerCu, kCostLdsStatic);
   hipLaunchKernelGGL(cost_four_waves(c) ? k_random_proposals : k_random_proposals_w3, dim3(round8(tiles), nd),
-                     dim3(kCostBlock), lds, c->stream, V, c->rank.as<int>(), tilesX, tiles);
+                     dim3(kCostBlock), lds, c->stream, V, c->w.rank.as<int>(), tilesX, tiles);
   KCHECK(c);
   return 0;
 }
@@ -704,7 +747,7 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   Span sp(c, ST_PINGPONG, L);
   LevelView V = make_view(c, ST_PINGPONG, dst0, nd);
   const size_t n = (size_t)V.W * V.H;
-  HIPCHK(c, hipMemsetAsync(c->changed.as<uint8_t>() + (size_t)dst0 * n, 1, n * nd, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->w.changed.as<uint8_t>() + (size_t)dst0 * n, 1, n * nd, c->stream));
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->ppWaves, c->ldsPerCu, kCostLdsStatic);
@@ -712,13 +755,13 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   const auto kernel = c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3);
   for (int it = 1; it <= c->opt.ping_pong_iterations; ++it) {
     hipLaunchKernelGGL(kernel, dim3(round8(tiles), nd), dim3(kCostBlock), lds,
-                       c->stream, V, c->changed.as<uint8_t>(), c->dispRes.as<float>(), c->costRes.as<float>(), tilesX,
+                       c->stream, V, c->w.changed.as<uint8_t>(), c->w.dispRes.as<float>(), c->w.costRes.as<float>(), tilesX,
                        (int)(it == 1 && c->randomRanThisLevel && !c->noMemo));
     KCHECK(c);
     hipLaunchKernelGGL(k_ping_pong_commit, dim3(flat_grid(n * nd)), dim3(256), 0, c->stream,
-                       c->disparity.as<float>() + (size_t)dst0 * n, c->cost.as<float>() + (size_t)dst0 * n,
-                       c->dispRes.as<float>() + (size_t)dst0 * n, c->costRes.as<float>() + (size_t)dst0 * n,
-                       c->changed.as<uint8_t>() + (size_t)dst0 * n, n * nd);
+                       c->w.disparity.as<float>() + (size_t)dst0 * n, c->w.cost.as<float>() + (size_t)dst0 * n,
+                       c->w.dispRes.as<float>() + (size_t)dst0 * n, c->w.costRes.as<float>() + (size_t)dst0 * n,
+                       c->w.changed.as<uint8_t>() + (size_t)dst0 * n, n * nd);
     KCHECK(c);
   }
   // cost / confidence now belong to ping-pong's result (+inf where every candidate was rejected): the
@@ -748,9 +791,9 @@ int run_mismatches(derp_ctx* c) {
   LevelView V = make_view(c, ST_MISMATCH, 0, c->D);
   const size_t n = (size_t)V.W * V.H;
   hipLaunchKernelGGL(k_mismatch, dim3((V.W + 15) / 16, (V.H + 15) / 16, c->D), dim3(256), 256 * sizeof(float) * c->S,
-                     c->stream, V, c->dispRes.as<float>(), c->mismatchMask.as<uint8_t>());
+                     c->stream, V, c->w.dispRes.as<float>(), c->w.mismatchMask.as<uint8_t>());
   KCHECK(c);
-  HIPCHK(c, hipMemcpyAsync(c->disparity.p, c->dispRes.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->w.disparity.p, c->w.dispRes.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -774,11 +817,11 @@ int run_bilateral(derp_ctx* c) {
   // weights passed (B, G, R) = (0.5, 1, 1) — Derp.cpp:893-896, Derp.h:44-48; sigma 0.005
   const int radius = bilateral_radius(L);
   hipLaunchKernelGGL(k_joint_bilateral<true>, dim3((W + 15) / 16, (H + 15) / 16, c->D), dim3(256),
-                     bilateral_lds_bytes(radius), c->stream, c->disparity.as<float>(),
-                     (const void*)c->pyrColor[L].as<ushort4>(), c->maskAnd.as<uint8_t>(), W, H, radius, 0.005f, 0.5f,
-                     1.0f, 1.0f, c->tmpF.as<float>(), n, n, c->dst2src.as<int>());
+                     bilateral_lds_bytes(radius), c->stream, c->w.disparity.as<float>(),
+                     (const void*)c->frame().color[L].as<ushort4>(), c->w.maskAnd.as<uint8_t>(), W, H, radius, 0.005f, 0.5f,
+                     1.0f, 1.0f, c->w.tmpF.as<float>(), n, n, c->dst2src.as<int>());
   KCHECK(c);
-  HIPCHK(c, hipMemcpyAsync(c->disparity.p, c->tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->w.disparity.p, c->w.tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -788,12 +831,12 @@ int run_median(derp_ctx* c, bool fuseMaskFov) {
   c->randomRanThisLevel = false;  // the working disparity changes: cost[] no longer matches it
   const int W = c->LW[L], H = c->LH[L];
   const size_t n = (size_t)W * H;
-  hipLaunchKernelGGL(k_masked_median, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->disparity.as<float>(),
-                     c->opt.use_foreground_masks ? c->pyrBg[L].as<float>() : (const float*)nullptr,
-                     c->maskAnd.as<uint8_t>(), W, H, 1, c->tmpF.as<float>(), n,
-                     fuseMaskFov ? c->fovMask.as<uint8_t>() : (const uint8_t*)nullptr);
+  hipLaunchKernelGGL(k_masked_median, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->w.disparity.as<float>(),
+                     c->opt.use_foreground_masks ? c->frame().bg[L].as<float>() : (const float*)nullptr,
+                     c->w.maskAnd.as<uint8_t>(), W, H, 1, c->w.tmpF.as<float>(), n,
+                     fuseMaskFov ? c->w.fovMask.as<uint8_t>() : (const uint8_t*)nullptr);
   KCHECK(c);
-  HIPCHK(c, hipMemcpyAsync(c->disparity.p, c->tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->w.disparity.p, c->w.tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -801,8 +844,8 @@ int run_mask_fov(derp_ctx* c) {
   const int L = c->cur;
   Span sp(c, ST_MASKFOV, L);
   const size_t n = npx(c, L) * c->D;
-  hipLaunchKernelGGL(k_mask_fov, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->disparity.as<float>(),
-                     c->fovMask.as<uint8_t>(), n);
+  hipLaunchKernelGGL(k_mask_fov, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->w.disparity.as<float>(),
+                     c->w.fovMask.as<uint8_t>(), n);
   KCHECK(c);
   return 0;
 }
@@ -835,44 +878,44 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   TRY(compute_fov_and_masks(c, level));
   {
     Span sp(c, ST_VARIANCE, level);
-    hipLaunchKernelGGL(k_variance, grid2d(W, H, c->S, kBlk2d), kBlk2d, 0, c->stream, c->pyrColor[level].as<ushort4>(),
-                       W, H, c->srcVar.as<float>());
+    hipLaunchKernelGGL(k_variance, grid2d(W, H, c->S, kBlk2d), kBlk2d, 0, c->stream, c->frame().color[level].as<ushort4>(),
+                       W, H, c->w.srcVar.as<float>());
     KCHECK(c);
   }
   {
     Span sp(c, ST_OWN_BIAS, level);
     hipLaunchKernelGGL(k_blur3_u16, blur_grid(W, H, c->S), kBlurBlk, 0, c->stream,
-                       c->pyrColor[level].as<ushort4>(), 0, c->ownBias.as<ushort4>(), 0, W, H, n, n);
+                       c->frame().color[level].as<ushort4>(), 0, c->w.ownBias.as<ushort4>(), 0, W, H, n, n);
     KCHECK(c);
   }
   // fresh PyramidLevel: disparity / cost / confidence start at 0 (PyramidLevel.h:209-221)
-  HIPCHK(c, hipMemsetAsync(c->cost.p, 0, n * c->D * sizeof(float), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->confidence.p, 0, n * c->D * sizeof(float), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->mismatchMask.p, 0, n * c->D, c->stream));
-  if (level < c->numLevels - 1 && !c->haveDisp[level + 1] && !buildAllTables) {
+  HIPCHK(c, hipMemsetAsync(c->w.cost.p, 0, n * c->D * sizeof(float), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->w.confidence.p, 0, n * c->D * sizeof(float), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->w.mismatchMask.p, 0, n * c->D, c->stream));
+  if (level < c->numLevels - 1 && !c->frame().haveDisp[level + 1] && !buildAllTables) {
     return fail(c, "Missing disparity of level %d needed to start level %d", level + 1, level);
   }
-  if (level < c->numLevels - 1 && c->haveDisp[level + 1]) {
+  if (level < c->numLevels - 1 && c->frame().haveDisp[level + 1]) {
     Span sp(c, ST_UPSAMPLE, level);
     const int sw = c->LW[level + 1], sh = c->LH[level + 1];
     if (!c->opt.use_foreground_masks) {
-      TRY(upsample_lanczos_dev(c, c->pyrDisp[level + 1].as<float>(), sw, sh, c->disparity.as<float>(), W, H, c->D,
+      TRY(upsample_lanczos_dev(c, c->frame().disp[level + 1].as<float>(), sw, sh, c->w.disparity.as<float>(), W, H, c->D,
                                (size_t)sw * sh, n));
     } else {
       // masks = fov & fg at both sizes (UpsampleDisparityLib.cpp:163-179); coarse fov&fg recomputed into tmpF bytes
-      ALLOC(c, c->staging, (size_t)sw * sh * c->D);
+      ALLOC(c, c->w.staging, (size_t)sw * sh * c->D);
       hipLaunchKernelGGL(k_fov_mask, grid2d(sw, sh, c->D, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>(), sw, sh,
-                         c->staging.as<uint8_t>());
+                         c->w.staging.as<uint8_t>());
       KCHECK(c);
       hipLaunchKernelGGL(k_and_masks, dim3(flat_grid((size_t)sw * sh), c->D), dim3(256), 0, c->stream,
-                         c->staging.as<uint8_t>(), c->pyrFg[level + 1].as<uint8_t>(), c->dst2src.as<int>(), 0,
-                         (size_t)sw * sh, c->staging.as<uint8_t>());
+                         c->w.staging.as<uint8_t>(), c->frame().fg[level + 1].as<uint8_t>(), c->dst2src.as<int>(), 0,
+                         (size_t)sw * sh, c->w.staging.as<uint8_t>());
       KCHECK(c);
-      TRY(upsample_masked_dev(c, c->pyrDisp[level + 1].as<float>(), c->staging.as<uint8_t>(), sw, sh,
-                              c->maskAnd.as<uint8_t>(), c->pyrBg[level].as<float>(), c->disparity.as<float>(), W, H, c->D));
+      TRY(upsample_masked_dev(c, c->frame().disp[level + 1].as<float>(), c->w.staging.as<uint8_t>(), sw, sh,
+                              c->w.maskAnd.as<uint8_t>(), c->frame().bg[level].as<float>(), c->w.disparity.as<float>(), W, H, c->D));
     }
   } else {
-    HIPCHK(c, hipMemsetAsync(c->disparity.p, 0, n * c->D * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->w.disparity.p, 0, n * c->D * sizeof(float), c->stream));
   }
   // table budget -> dst batch. When the buffers already hold every destination's tables of this level (the
   // steady state of a sequence: same levels frame after frame) there is nothing to ask the runtime.
@@ -885,13 +928,13 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
     const size_t wpAll = (size_t)(W + 2 * kPadW) * (H + 2 * kPadW) * (c->S - 1) * c->D * sizeof(float2);
     const size_t cpAll = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC) * (c->S - 1) * c->D * sizeof(ushort4);
     const size_t ipAll = (size_t)W * H * (c->S - 1) * c->D * sizeof(float2);
-    const bool resident = c->projWarp.bytes >= wpAll && c->projColor.bytes >= cpAll && c->projBias.bytes >= cpAll &&
+    const bool resident = c->projWarp.bytes >= wpAll && c->w.projColor.bytes >= cpAll && c->w.projBias.bytes >= cpAll &&
         (!invAll || c->projWarpInv.bytes >= ipAll) && !getenv("DERP_TABLE_BUDGET_GB") &&
-        (!DERP_RANDOM_TILED || c->projColorT.bytes >= tiled_plane(W, H) * (c->S - 1) * c->D * sizeof(ushort4));
+        (!DERP_RANDOM_TILED || c->w.projColorT.bytes >= tiled_plane(W, H) * (c->S - 1) * c->D * sizeof(ushort4));
     if (!resident) {
       size_t freeB = 0, totalB = 0;
       HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
-      size_t budget = freeB + c->projWarp.bytes + c->projColor.bytes + c->projBias.bytes + c->projWarpInv.bytes + c->projColorT.bytes;
+      size_t budget = freeB + c->projWarp.bytes + c->w.projColor.bytes + c->w.projBias.bytes + c->projWarpInv.bytes + c->w.projColorT.bytes;
       if (const char* e = getenv("DERP_TABLE_BUDGET_GB")) {
         budget = std::min<size_t>(budget, (size_t)(atof(e) * (1ull << 30)));
       } else {
@@ -914,13 +957,13 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   c->DB = DB;
   const size_t wp = (size_t)(W + 2 * kPadW) * (H + 2 * kPadW), cp = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC);
   ALLOC(c, c->projWarp, (size_t)DB * (c->S - 1) * wp * sizeof(float2));
-  ALLOC(c, c->projColor, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
-  ALLOC(c, c->projBias, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
+  ALLOC(c, c->w.projColor, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
+  ALLOC(c, c->w.projBias, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
   if (needInv) {
     ALLOC(c, c->projWarpInv, (size_t)DB * (c->S - 1) * n * sizeof(float2));
   }
   if (DERP_RANDOM_TILED) {
-    ALLOC(c, c->projColorT, (size_t)DB * (c->S - 1) * tiled_plane(W, H) * sizeof(ushort4));
+    ALLOC(c, c->w.projColorT, (size_t)DB * (c->S - 1) * tiled_plane(W, H) * sizeof(ushort4));
   }
   c->tablesValid = false;
   c->randomRanThisLevel = false;
@@ -938,9 +981,9 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
 
 int level_end(derp_ctx* c) {
   const int L = c->cur;
-  HIPCHK(c, hipMemcpyAsync(c->pyrDisp[L].p, c->disparity.p, npx(c, L) * c->D * sizeof(float),
+  HIPCHK(c, hipMemcpyAsync(c->frame().disp[L].p, c->w.disparity.p, npx(c, L) * c->D * sizeof(float),
                            hipMemcpyDeviceToDevice, c->stream));
-  c->haveDisp[L] = 1;
+  c->frame().haveDisp[L] = 1;
   return 0;
 }
 
@@ -989,78 +1032,84 @@ int upload_tmp(derp_ctx* c, DevBuf& buf, const T* host, size_t count) {
   return 0;
 }
 
+// The host-pointer entry points copy with plain hipMemcpy: the context's stream is non-blocking, so these null-stream
+// copies do not order against it — a kernel's input is complete when the call returns, its output is read after a
+// synchronise.
+int upload_sync(derp_ctx* c, DevBuf& buf, const void* host, size_t bytes) {
+  ALLOC(c, buf, bytes);
+  HIPCHK(c, hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+int download_sync(derp_ctx* c, void* host, const void* dev, size_t bytes) {
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
 
-// HBM-resident pyramid of one frame (colour, fg masks, background disparity, result per level)
-int alloc_pyramid(derp_ctx* c, std::vector<DevBuf>& color, std::vector<DevBuf>& fg, std::vector<DevBuf>& bg,
-                  std::vector<DevBuf>& disp, std::vector<char>& haveBg, std::vector<char>& haveDisp) {
+// the buffers of one frame's pyramid at the context's geometry
+int alloc_pyramid(derp_ctx* c, FramePyramid& f) {
   const int num_levels = c->numLevels;
-  color.resize(num_levels);
-  fg.resize(num_levels);
-  bg.resize(num_levels);
-  disp.resize(num_levels);
-  haveBg.assign(num_levels, 0);
-  haveDisp.assign(num_levels, 0);
+  f.color.resize(num_levels);
+  f.fg.resize(num_levels);
+  f.bg.resize(num_levels);
+  f.disp.resize(num_levels);
+  f.haveBg.assign(num_levels, 0);
+  f.haveDisp.assign(num_levels, 0);
   for (int l = 0; l < num_levels; ++l) {
     const size_t n = npx(c, l);
     if (n == 0) {
       continue;  // level not present / not needed by this run
     }
-    ALLOC(c, color[l], n * c->S * sizeof(ushort4));
-    ALLOC(c, fg[l], n * c->S);
-    ALLOC(c, bg[l], n * c->D * sizeof(float));
-    ALLOC(c, disp[l], n * c->D * sizeof(float));
-    HIPCHK(c, hipMemsetAsync(fg[l].p, 1, n * c->S, c->stream));  // generateAllPassMasks
-    HIPCHK(c, hipMemsetAsync(bg[l].p, 0, n * c->D * sizeof(float), c->stream));
+    ALLOC(c, f.color[l], n * c->S * sizeof(ushort4));
+    ALLOC(c, f.fg[l], n * c->S);
+    ALLOC(c, f.bg[l], n * c->D * sizeof(float));
+    ALLOC(c, f.disp[l], n * c->D * sizeof(float));
+    HIPCHK(c, hipMemsetAsync(f.fg[l].p, 1, n * c->S, c->stream));  // generateAllPassMasks
+    HIPCHK(c, hipMemsetAsync(f.bg[l].p, 0, n * c->D * sizeof(float), c->stream));
   }
   return 0;
 }
 
-// make `slot` the frame the pyramid members refer to
+// the per-frame working buffers of a level of up to `n` pixels (the colour tables and scratch grow where they are used)
+int alloc_work_set(derp_ctx* c, WorkSet& w, size_t n) {
+  ALLOC(c, w.srcVar, n * c->S * sizeof(float));
+  ALLOC(c, w.ownBias, n * c->S * sizeof(ushort4));
+  ALLOC(c, w.fovMask, n * c->D);
+  ALLOC(c, w.maskAnd, n * c->D);
+  for (DevBuf* b : {&w.disparity, &w.cost, &w.confidence, &w.dispRes, &w.costRes, &w.tmpF, &w.rank}) {
+    ALLOC(c, *b, n * c->D * sizeof(float));
+  }
+  ALLOC(c, w.changed, n * c->D);
+  ALLOC(c, w.mismatchMask, n * c->D);
+  ALLOC(c, w.pairCount, n * c->D);
+  return 0;
+}
+
+// make `slot` the frame the level loop works on
 int select_frame(derp_ctx* c, int slot) {
-  if (slot < 0 || slot >= (int)c->parked.size()) {
-    return fail(c, "frame slot %d out of range [0, %d)", slot, (int)c->parked.size());
+  if (slot < 0 || slot >= (int)c->frames.size()) {
+    return fail(c, "frame slot %d out of range [0, %d)", slot, (int)c->frames.size());
   }
-  if (slot == c->curSlot) {
-    return 0;
+  if (slot != c->curSlot) {
+    c->curSlot = slot;
+    c->cur = -1;  // working buffers belong to the previously selected frame
   }
-  auto swap_with = [&](derp_ctx::FrameSlot& fs) {
-    std::swap(fs.pyrColor, c->pyrColor);
-    std::swap(fs.pyrFg, c->pyrFg);
-    std::swap(fs.pyrBg, c->pyrBg);
-    std::swap(fs.pyrDisp, c->pyrDisp);
-    std::swap(fs.haveBg, c->haveBg);
-    std::swap(fs.haveDisp, c->haveDisp);
-  };
-  swap_with(c->parked[c->curSlot]);  // park the active frame
-  swap_with(c->parked[slot]);        // activate the requested one
-  c->curSlot = slot;
-  c->cur = -1;  // working buffers belong to the previously selected frame
   return 0;
 }
 
 // exchange the context's per-frame working set (and stream) with lane `i`'s: applied twice it is the identity
 void lane_swap(derp_ctx* c, int i) {
-  derp_ctx::WorkLane& w = *c->lanes[i];
-  std::swap(c->stream, w.stream);
-  std::swap(c->colorTablesCleanLevel, w.colorTablesCleanLevel);
-  DevBuf* mine[] = {&c->srcVar, &c->ownBias, &c->fovMask, &c->maskAnd, &c->disparity, &c->cost, &c->confidence, &c->dispRes,
-                    &c->costRes, &c->changed, &c->tmpF, &c->rank, &c->mismatchMask, &c->pairCount, &c->tileSeen, &c->projColor,
-                    &c->projBias, &c->projColorT, &c->bruteCost, &c->bruteConf, &c->lanczosTmp, &c->staging, &c->stagingB};
-  DevBuf* theirs[] = {&w.srcVar, &w.ownBias, &w.fovMask, &w.maskAnd, &w.disparity, &w.cost, &w.confidence, &w.dispRes,
-                      &w.costRes, &w.changed, &w.tmpF, &w.rank, &w.mismatchMask, &w.pairCount, &w.tileSeen, &w.projColor,
-                      &w.projBias, &w.projColorT, &w.bruteCost, &w.bruteConf, &w.lanczosTmp, &w.staging, &w.stagingB};
-  for (size_t k = 0; k < sizeof(mine) / sizeof(mine[0]); ++k) {
-    std::swap(*mine[k], *theirs[k]);
-  }
+  std::swap(c->stream, c->lanes[i]->stream);
+  std::swap(c->w, c->lanes[i]->w);
 }
 
 // lanes 0 .. count - 1 exist and hold working buffers for a level of `n` pixels
 int lanes_prepare(derp_ctx* c, int count, size_t n) {
   while ((int)c->lanes.size() < count) {
-    auto* w = new derp_ctx::WorkLane();
-    c->lanes.push_back(w);
-    if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&w->done, hipEventDisableTiming) != hipSuccess) {
+    c->lanes.emplace_back(new WorkLane);
+    WorkLane& l = *c->lanes.back();
+    if (hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess) {
       return fail(c, "work lane: hipStreamCreate / hipEventCreate failed");
     }
   }
@@ -1068,17 +1117,7 @@ int lanes_prepare(derp_ctx* c, int count, size_t n) {
     HIPCHK(c, hipEventCreateWithFlags(&c->laneReady, hipEventDisableTiming));
   }
   for (int i = 0; i < count; ++i) {
-    derp_ctx::WorkLane& w = *c->lanes[i];
-    ALLOC(c, w.srcVar, n * c->S * sizeof(float));
-    ALLOC(c, w.ownBias, n * c->S * sizeof(ushort4));
-    ALLOC(c, w.fovMask, n * c->D);
-    ALLOC(c, w.maskAnd, n * c->D);
-    for (DevBuf* b : {&w.disparity, &w.cost, &w.confidence, &w.dispRes, &w.costRes, &w.tmpF, &w.rank}) {
-      ALLOC(c, *b, n * c->D * sizeof(float));
-    }
-    ALLOC(c, w.changed, n * c->D);
-    ALLOC(c, w.mismatchMask, n * c->D);
-    ALLOC(c, w.pairCount, n * c->D);
+    TRY(alloc_work_set(c, c->lanes[i]->w, n));
   }
   return 0;
 }
@@ -1148,39 +1187,8 @@ int temporal_launch(derp_ctx* c, const void* const* guides, const float* const* 
 
 }  // namespace
 
-// ---- derp_render_*: SimpleMeshRenderer's scene (derp_render.h) ----
-struct SmrCam {
-  int dw = 0, dh = 0, tw = 0, th = 0;  // disparity (mesh) and colour texture sizes
-  CanopyMips Mc, Md;                   // mip geometry of the colour texture and of the disparity-colour texture
-  DevBuf vert, eyeVert, texColor, texDisp;
-  float eyeIpd = 0.0f;  // ipdm eyeVert was computed for (0: none yet)
-};
-struct SmrState {
-  std::vector<SmrCam> cams;
-  bool haveColor = false;
-  bool dispValid = false;
-  float dispPos[3] = {0, 0, 0};  // position the disparity colours were computed for
-  DevBuf zbuf, acc, big, nBig, cube, img, img2, tabs, back, equi, fetch, staging;
-};
-
+// ---- derp_render_*: SimpleMeshRenderer (derp_render.h) ----
 namespace {
-
-void smr_free(derp_ctx* c) {
-  if (!c->smr) {
-    return;
-  }
-  for (SmrCam& k : c->smr->cams) {
-    for (DevBuf* b : {&k.vert, &k.eyeVert, &k.texColor, &k.texDisp}) {
-      b->release();
-    }
-  }
-  SmrState& S = *c->smr;
-  for (DevBuf* b : {&S.zbuf, &S.acc, &S.big, &S.nBig, &S.cube, &S.img, &S.img2, &S.tabs, &S.back, &S.equi, &S.fetch, &S.staging}) {
-    b->release();
-  }
-  delete c->smr;
-  c->smr = nullptr;
-}
 
 // glGenerateMipmap's level sizes (halve, round down, never below 1); false when the chain does not fit
 bool smr_mips(int w, int h, CanopyMips& M, size_t& texels) {
@@ -1472,22 +1480,13 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
     return 1;
   }
   *out = nullptr;
-  derp_ctx* c = new derp_ctx;
+  std::unique_ptr<derp_ctx> owner(new derp_ctx);  // until success: an early return frees what was allocated so far
+  derp_ctx* c = owner.get();
   derp_options_default(&c->opt);
   memset(c->accMs, 0, sizeof c->accMs);
   memset(c->accLaunch, 0, sizeof c->accLaunch);
   auto bail = [&](const std::string& m) {
     g_create_error = m;
-    for (DevBuf* b : {&c->camsSrc, &c->camsDst, &c->dst2src, &c->counters}) {
-      b->release();
-    }
-    if (c->stream) {
-      (void)hipStreamDestroy(c->stream);
-    }
-    if (c->copyStream) {
-      (void)hipStreamDestroy(c->copyStream);
-    }
-    delete c;
     return 1;
   };
   if (n_src <= 0 || n_dst <= 0) {
@@ -1529,13 +1528,9 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
   }
   c->noTemporalTile = getenv("DERP_NO_TEMPORAL_TILE") != nullptr;
   c->noBlankSkip = getenv("DERP_NO_BLANK_SKIP") != nullptr;
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking) != hipSuccess) {
-    return bail("hipStreamCreate failed");
-  }
   c->S = n_src;
   c->D = n_dst;
-  c->parked.assign(1, derp_ctx::FrameSlot());
+  c->frames.resize(1);
   c->camsSrcH.resize(n_src);
   c->camsDstH.resize(n_dst);
   for (int i = 0; i < n_src; ++i) {
@@ -1571,11 +1566,19 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
       c->dst2src.ensure(sizeof(int) * n_dst) || c->counters.ensure(sizeof(unsigned long long) * ST_COUNT * kMaxLevels * 4)) {
     return bail("out of device memory");
   }
+  // the streams last: they are torn down by derp_destroy alone, and nothing after them fails
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    return bail("hipStreamCreate failed");
+  }
+  if (hipStreamCreateWithFlags(&c->copyStream, hipStreamNonBlocking) != hipSuccess) {
+    (void)hipStreamDestroy(c->stream);
+    return bail("hipStreamCreate failed");
+  }
   (void)hipMemcpy(c->camsSrc.p, c->camsSrcH.data(), sizeof(Cam) * n_src, hipMemcpyHostToDevice);
   (void)hipMemcpy(c->camsDst.p, c->camsDstH.data(), sizeof(Cam) * n_dst, hipMemcpyHostToDevice);
   (void)hipMemcpy(c->dst2src.p, c->dst2srcH.data(), sizeof(int) * n_dst, hipMemcpyHostToDevice);
   (void)hipMemset(c->counters.p, 0, c->counters.bytes);
-  *out = c;
+  *out = owner.release();  // (the unique_ptr's: the caller owns the context now)
   return 0;
 }
 
@@ -1585,62 +1588,20 @@ void derp_destroy(derp_ctx* c) {
   }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  for (auto& l : c->lanes) {
+    (void)hipStreamSynchronize(l->stream);
+  }
   drain_spans(c);
-  for (auto* v : {&c->pyrColor, &c->pyrFg, &c->pyrBg, &c->pyrDisp}) {
-    for (auto& b : *v) {
-      b.release();
-    }
-  }
-  for (auto& fs : c->parked) {
-    for (auto* v : {&fs.pyrColor, &fs.pyrFg, &fs.pyrBg, &fs.pyrDisp}) {
-      for (auto& b : *v) {
-        b.release();
-      }
-    }
-  }
-  c->devMask.release();
-  for (DevBuf* b : {&c->camsSrc, &c->camsDst, &c->dst2src, &c->srcVar, &c->ownBias, &c->fovMask, &c->maskAnd,
-                    &c->disparity, &c->cost, &c->confidence, &c->dispRes, &c->costRes, &c->changed, &c->tmpF, &c->rank, &c->mismatchMask, &c->pairCount,
-                    &c->projWarp, &c->projColor, &c->projBias, &c->projColorT, &c->projWarpInv, &c->temporalCarry, &c->tileSeen, &c->rayDir, &c->behind, &c->bruteCost, &c->bruteConf, &c->lanczosTmp,
-                    &c->staging, &c->stagingB, &c->counters, &c->spiral}) {
-    b->release();
-  }
-  for (auto& kv : c->lanczos) {
-    kv.second->ofs.release();
-    kv.second->coef.release();
-    delete kv.second;
-  }
-  for (auto& kv : c->areaTabs) {
-    kv.second->start.release();
-    kv.second->si.release();
-    kv.second->alpha.release();
-    delete kv.second;
-  }
-  c->fullFrame.release();
-  c->rephotoColor.release();
-  c->rephotoDisp.release();
-  c->copyStaging.release();
-  for (DevBuf* b : {&c->cnVert, &c->cnRgba, &c->cnZ, &c->cnAcc, &c->cnOut, &c->cnBig, &c->cnNBig}) {
-    b->release();
-  }
-  smr_free(c);
-  for (derp_ctx::WorkLane* w : c->lanes) {
-    (void)hipStreamSynchronize(w->stream);
-    for (DevBuf* b : {&w->srcVar, &w->ownBias, &w->fovMask, &w->maskAnd, &w->disparity, &w->cost, &w->confidence, &w->dispRes,
-                      &w->costRes, &w->changed, &w->tmpF, &w->rank, &w->mismatchMask, &w->pairCount, &w->tileSeen, &w->projColor,
-                      &w->projBias, &w->projColorT, &w->bruteCost, &w->bruteConf, &w->lanczosTmp, &w->staging, &w->stagingB}) {
-      b->release();
-    }
-    (void)hipStreamDestroy(w->stream);
-    (void)hipEventDestroy(w->done);
-    delete w;
+  for (auto& l : c->lanes) {
+    (void)hipStreamDestroy(l->stream);
+    (void)hipEventDestroy(l->done);
   }
   if (c->laneReady) {
     (void)hipEventDestroy(c->laneReady);
   }
   (void)hipStreamDestroy(c->stream);
   (void)hipStreamDestroy(c->copyStream);
-  delete c;
+  delete c;  // every device buffer goes with its owner
 }
 
 const char* derp_last_error(const derp_ctx* c) {
@@ -1672,31 +1633,16 @@ int derp_set_pyramid(derp_ctx* c, int num_levels, const int* widths, const int* 
   c->heightFull = height_full;
   c->LW.assign(widths, widths + num_levels);
   c->LH.assign(heights, heights + num_levels);
-  // a new geometry drops every frame slot but the selected one (their buffers have the old sizes)
-  for (auto& fs : c->parked) {
-    for (auto* v : {&fs.pyrColor, &fs.pyrFg, &fs.pyrBg, &fs.pyrDisp}) {
-      for (auto& b : *v) {
-        b.release();
-      }
-    }
-  }
-  c->parked.assign(1, derp_ctx::FrameSlot());
+  // a new geometry drops every frame slot (their buffers have the old sizes) and starts again with slot 0
+  c->frames.clear();
+  c->frames.resize(1);
   c->curSlot = 0;
-  TRY(alloc_pyramid(c, c->pyrColor, c->pyrFg, c->pyrBg, c->pyrDisp, c->haveBg, c->haveDisp));
+  TRY(alloc_pyramid(c, c->frame()));
   size_t nmax = 0;
   for (int l = 0; l < num_levels; ++l) {
     nmax = std::max(nmax, npx(c, l));
   }
-  ALLOC(c, c->srcVar, nmax * c->S * sizeof(float));
-  ALLOC(c, c->ownBias, nmax * c->S * sizeof(ushort4));
-  ALLOC(c, c->fovMask, nmax * c->D);
-  ALLOC(c, c->maskAnd, nmax * c->D);
-  for (DevBuf* b : {&c->disparity, &c->cost, &c->confidence, &c->dispRes, &c->costRes, &c->tmpF, &c->rank}) {
-    ALLOC(c, *b, nmax * c->D * sizeof(float));
-  }
-  ALLOC(c, c->changed, nmax * c->D);
-  ALLOC(c, c->mismatchMask, nmax * c->D);
-  ALLOC(c, c->pairCount, nmax * c->D);
+  TRY(alloc_work_set(c, c->w, nmax));
   c->cur = -1;
   c->warpCachedLevel = -1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1712,18 +1658,10 @@ int derp_set_frame_slots(derp_ctx* c, int n_slots) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   TRY(select_frame(c, 0));
-  for (int k = (int)c->parked.size() - 1; k >= n_slots; --k) {
-    for (auto* v : {&c->parked[k].pyrColor, &c->parked[k].pyrFg, &c->parked[k].pyrBg, &c->parked[k].pyrDisp}) {
-      for (auto& b : *v) {
-        b.release();
-      }
-    }
-  }
-  const int had = (int)c->parked.size();
-  c->parked.resize(n_slots);
+  const int had = (int)c->frames.size();
+  c->frames.resize(n_slots);  // growing moves the pyramids that exist: their buffers stay where they are
   for (int k = had; k < n_slots; ++k) {
-    derp_ctx::FrameSlot& fs = c->parked[k];
-    TRY(alloc_pyramid(c, fs.pyrColor, fs.pyrFg, fs.pyrBg, fs.pyrDisp, fs.haveBg, fs.haveDisp));
+    TRY(alloc_pyramid(c, c->frames[k]));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -1741,7 +1679,7 @@ int derp_frame_slots(const derp_ctx* c, int* n_slots, int* selected) {
     return 1;
   }
   if (n_slots) {
-    *n_slots = (int)c->parked.size();
+    *n_slots = (int)c->frames.size();
   }
   if (selected) {
     *selected = c->curSlot;
@@ -1789,9 +1727,9 @@ int derp_upload_color(derp_ctx* c, int level, int s, const uint16_t* bgr) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = npx(c, level);
-  TRY(upload_tmp(c, c->staging, bgr, n * 3));
-  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->staging.as<uint16_t>(),
-                     c->pyrColor[level].as<ushort4>() + (size_t)s * n, n);
+  TRY(upload_tmp(c, c->w.staging, bgr, n * 3));
+  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->w.staging.as<uint16_t>(),
+                     c->frame().color[level].as<ushort4>() + (size_t)s * n, n);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));  // staging buffer is reused by the next upload
   if (c->warpCachedLevel == level) {
@@ -1807,7 +1745,7 @@ int derp_upload_foreground_mask(derp_ctx* c, int level, int s, const uint8_t* ma
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = npx(c, level);
-  HIPCHK(c, hipMemcpy(c->pyrFg[level].as<uint8_t>() + (size_t)s * n, mask, n, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->frame().fg[level].as<uint8_t>() + (size_t)s * n, mask, n, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1818,8 +1756,8 @@ int derp_upload_background_disparity(derp_ctx* c, int level, int d, const float*
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = npx(c, level);
-  HIPCHK(c, hipMemcpy(c->pyrBg[level].as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
-  c->haveBg[level] = 1;
+  HIPCHK(c, hipMemcpy(c->frame().bg[level].as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
+  c->frame().haveBg[level] = 1;
   return 0;
 }
 
@@ -1830,8 +1768,8 @@ int derp_upload_disparity(derp_ctx* c, int level, int d, const float* disp) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = npx(c, level);
-  HIPCHK(c, hipMemcpy(c->pyrDisp[level].as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
-  c->haveDisp[level] = 1;
+  HIPCHK(c, hipMemcpy(c->frame().disp[level].as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
+  c->frame().haveDisp[level] = 1;
   return 0;
 }
 
@@ -1878,12 +1816,12 @@ int derp_download_disparity(derp_ctx* c, int level, int d, float* disparity) {
   if (d < 0 || d >= c->D || !disparity) {
     return fail(c, "bad destination index / null output");
   }
-  if (!c->haveDisp[level]) {
+  if (!c->frame().haveDisp[level]) {
     return fail(c, "level %d has not been processed", level);
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t n = npx(c, level);
-  HIPCHK(c, hipMemcpy(disparity, c->pyrDisp[level].as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(disparity, c->frame().disp[level].as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1895,10 +1833,10 @@ int derp_download_cost(derp_ctx* c, int d, float* cost, float* confidence) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t n = npx(c, c->cur);
   if (cost) {
-    HIPCHK(c, hipMemcpy(cost, c->cost.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cost, c->w.cost.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
   }
   if (confidence) {
-    HIPCHK(c, hipMemcpy(confidence, c->confidence.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(confidence, c->w.confidence.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -1956,7 +1894,7 @@ int derp_set_level_disparity(derp_ctx* c, int d, const float* disp) {
   }
   const size_t n = npx(c, c->cur);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(c->disparity.as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->w.disparity.as<float>() + (size_t)d * n, disp, n * sizeof(float), hipMemcpyHostToDevice));
   c->randomRanThisLevel = false;  // cost[] no longer belongs to the working disparity
   return 0;
 }
@@ -1967,7 +1905,7 @@ int derp_get_level_disparity(derp_ctx* c, int d, float* disp) {
   }
   const size_t n = npx(c, c->cur);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(disp, c->disparity.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(disp, c->w.disparity.as<float>() + (size_t)d * n, n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1978,19 +1916,19 @@ int derp_cost_map(derp_ctx* c, int d, const float* disp, float* cost, float* con
   }
   const int L = c->cur;
   const size_t n = npx(c, L);
-  TRY(upload_tmp(c, c->staging, disp, n));
-  ALLOC(c, c->stagingB, 2 * n * sizeof(float));
-  HIPCHK(c, hipMemsetAsync(c->stagingB.p, 0xff, 2 * n * sizeof(float), c->stream));  // NaN fill
+  TRY(upload_tmp(c, c->w.staging, disp, n));
+  ALLOC(c, c->w.stagingB, 2 * n * sizeof(float));
+  HIPCHK(c, hipMemsetAsync(c->w.stagingB.p, 0xff, 2 * n * sizeof(float), c->stream));  // NaN fill
   LevelView V = make_view(c, ST_PINGPONG, 0, c->D);
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = kCostLdsPerSrc * (size_t)(c->S);
-  hipLaunchKernelGGL(k_cost_map, dim3(tiles), dim3(kCostBlock), lds, c->stream, V, d, c->staging.as<float>(),
-                     c->stagingB.as<float>(), c->stagingB.as<float>() + n, tilesX);
+  hipLaunchKernelGGL(k_cost_map, dim3(tiles), dim3(kCostBlock), lds, c->stream, V, d, c->w.staging.as<float>(),
+                     c->w.stagingB.as<float>(), c->w.stagingB.as<float>() + n, tilesX);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(cost, c->stagingB.p, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(confidence, c->stagingB.as<float>() + n, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cost, c->w.stagingB.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(confidence, c->w.stagingB.as<float>() + n, n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1998,8 +1936,8 @@ int derp_debug_atan2_ypos(derp_ctx* c, const double* y, const double* x, double*
   if (!c || !y || !x || !out) {
     return fail(c, "bad arguments");
   }
-  ALLOC(c, c->staging, 3 * n * sizeof(double));
-  double* d = c->staging.as<double>();
+  ALLOC(c, c->w.staging, 3 * n * sizeof(double));
+  double* d = c->w.staging.as<double>();
   HIPCHK(c, hipMemcpyAsync(d, y, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d + n, x, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_debug_atan2_ypos, dim3(flat_grid(n)), dim3(256), 0, c->stream, d, d + n, d + 2 * n, n);
@@ -2016,8 +1954,8 @@ int derp_debug_fp64(derp_ctx* c, int op, const double* a, const double* b, doubl
   if (n == 0) {
     return 0;
   }
-  ALLOC(c, c->staging, 3 * n * sizeof(double));
-  double* d = c->staging.as<double>();
+  ALLOC(c, c->w.staging, 3 * n * sizeof(double));
+  double* d = c->w.staging.as<double>();
   HIPCHK(c, hipMemcpyAsync(d, a, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d + n, op >= 2 ? b : a, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_debug_fp64, dim3(flat_grid(n)), dim3(256), 0, c->stream, op, d, d + n, d + 2 * n, n);
@@ -2034,8 +1972,8 @@ int derp_debug_sees(derp_ctx* c, int src, const double* xyz, size_t n, double* o
   if (n == 0) {
     return 0;
   }
-  ALLOC(c, c->staging, 9 * n * sizeof(double));
-  double* d = c->staging.as<double>();
+  ALLOC(c, c->w.staging, 9 * n * sizeof(double));
+  double* d = c->w.staging.as<double>();
   HIPCHK(c, hipMemcpyAsync(d, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_debug_sees, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->camsSrc.as<Cam>(), src, d, d + 3 * n, n);
   KCHECK(c);
@@ -2051,11 +1989,11 @@ int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
   const size_t n = (size_t)W * H;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (which == 4) {
-    HIPCHK(c, hipMemcpy(out, c->srcVar.as<float>() + (size_t)s * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->w.srcVar.as<float>() + (size_t)s * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   }
   if (which == 5) {
-    HIPCHK(c, hipMemcpy(out, c->fovMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->w.fovMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
     return 0;
   }
   if (d < 0 || d >= c->D || s < 0 || s >= c->S || s == c->dst2srcH[d]) {
@@ -2076,7 +2014,7 @@ int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
   if (which == 2 || which == 3) {
     const int PW = W + 2 * kPadC, PH = H + 2 * kPadC;
     std::vector<ushort4> tmp((size_t)PW * PH);
-    const ushort4* base = (which == 2 ? c->projColor.as<ushort4>() : c->projBias.as<ushort4>()) + tab * tmp.size();
+    const ushort4* base = (which == 2 ? c->w.projColor.as<ushort4>() : c->w.projBias.as<ushort4>()) + tab * tmp.size();
     HIPCHK(c, hipMemcpy(tmp.data(), base, tmp.size() * sizeof(ushort4), hipMemcpyDeviceToHost));
     uint16_t* o = reinterpret_cast<uint16_t*>(out);
     for (int y = 0; y < H; ++y) {
@@ -2110,12 +2048,12 @@ static int build_pyramid(derp_ctx* c, int kind, int index, int count, const void
     if (nl == 0) {
       continue;
     }
-    void* dst = kind == 0 ? (void*)(c->pyrColor[l].as<ushort4>() + (size_t)index * nl)
-        : kind == 1       ? (void*)(c->pyrFg[l].as<uint8_t>() + (size_t)index * nl)
-                          : (void*)(c->pyrBg[l].as<float>() + (size_t)index * nl);
+    void* dst = kind == 0 ? (void*)(c->frame().color[l].as<ushort4>() + (size_t)index * nl)
+        : kind == 1       ? (void*)(c->frame().fg[l].as<uint8_t>() + (size_t)index * nl)
+                          : (void*)(c->frame().bg[l].as<float>() + (size_t)index * nl);
     TRY(resize_area_dev(c, kind, c->fullFrame.p, w, h, dst, c->LW[l], c->LH[l], threshold));
     if (kind == 2) {
-      c->haveBg[l] = 1;
+      c->frame().haveBg[l] = 1;
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));  // fullFrame is reused by the next call
@@ -2136,12 +2074,12 @@ int derp_download_level_color(derp_ctx* c, int level, int src, uint16_t* bgr) {
     return fail(c, "bad source index / null output");
   }
   const size_t n = npx(c, level);
-  ALLOC(c, c->staging, n * 6);
+  ALLOC(c, c->w.staging, n * 6);
   hipLaunchKernelGGL(k_bgrx_to_bgr, dim3(flat_grid(n)), dim3(256), 0, c->stream,
-                     c->pyrColor[level].as<ushort4>() + (size_t)src * n, c->staging.as<uint16_t>(), n);
+                     c->frame().color[level].as<ushort4>() + (size_t)src * n, c->w.staging.as<uint16_t>(), n);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(bgr, c->staging.p, n * 6, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(bgr, c->w.staging.p, n * 6, hipMemcpyDeviceToHost));
   return 0;
 }
 int derp_download_level_mask(derp_ctx* c, int level, int src, uint8_t* mask) {
@@ -2151,7 +2089,7 @@ int derp_download_level_mask(derp_ctx* c, int level, int src, uint8_t* mask) {
   }
   const size_t n = npx(c, level);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(mask, c->pyrFg[level].as<uint8_t>() + (size_t)src * n, n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(mask, c->frame().fg[level].as<uint8_t>() + (size_t)src * n, n, hipMemcpyDeviceToHost));
   return 0;
 }
 int derp_download_level_background(derp_ctx* c, int level, int dst, float* disp) {
@@ -2161,7 +2099,7 @@ int derp_download_level_background(derp_ctx* c, int level, int dst, float* disp)
   }
   const size_t n = npx(c, level);
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(disp, c->pyrBg[level].as<float>() + (size_t)dst * n, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(disp, c->frame().bg[level].as<float>() + (size_t)dst * n, n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 // one image: kind 0 = BGR u16 x3, 1 = u8, 2 = f32, 3 = BGR f32 x3 (host in / host out)
@@ -2172,25 +2110,15 @@ int derp_resize_area(derp_ctx* c, int kind, const void* src, int w, int h, void*
   HIPCHK(c, hipSetDevice(c->device));
   const size_t elem = kind == 0 ? 6 : kind == 1 ? 1 : kind == 3 ? 12 : 4, n = (size_t)w * h, nd = (size_t)dw * dh;
   DevBuf in, out, out3;
-  int rc = 0;
-  if (in.ensure(n * elem) || out.ensure(nd * (kind == 0 ? 8 : elem)) || (kind == 0 && out3.ensure(nd * 6))) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(in.p, src, n * elem, hipMemcpyHostToDevice);
-    rc = resize_area_dev(c, kind, in.p, w, h, out.p, dw, dh, -1);
-    if (!rc && kind == 0) {
-      hipLaunchKernelGGL(k_bgrx_to_bgr, dim3(flat_grid(nd)), dim3(256), 0, c->stream, out.as<ushort4>(),
-                         out3.as<uint16_t>(), nd);
-    }
-    if (!rc && (hipStreamSynchronize(c->stream) != hipSuccess ||
-                hipMemcpy(dst, kind == 0 ? out3.p : out.p, nd * elem, hipMemcpyDeviceToHost) != hipSuccess)) {
-      rc = fail(c, "HIP error in derp_resize_area: %s", hipGetErrorString(hipGetLastError()));
-    }
+  TRY(upload_sync(c, in, src, n * elem));
+  ALLOC(c, out, nd * (kind == 0 ? 8 : elem));
+  TRY(resize_area_dev(c, kind, in.p, w, h, out.p, dw, dh, -1));
+  if (kind == 0) {
+    ALLOC(c, out3, nd * 6);
+    hipLaunchKernelGGL(k_bgrx_to_bgr, dim3(flat_grid(nd)), dim3(256), 0, c->stream, out.as<ushort4>(),
+                       out3.as<uint16_t>(), nd);
   }
-  for (DevBuf* b : {&in, &out, &out3}) {
-    b->release();
-  }
-  return rc;
+  return download_sync(c, dst, kind == 0 ? out3.p : out.p, nd * elem);
 }
 
 // ---- GenerateForegroundMasks (source/render/BackgroundSubtractionUtil.h:20-60) ----
@@ -2203,37 +2131,30 @@ int derp_generate_foreground_mask(derp_ctx* c, const uint16_t* template_bgr, con
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
   DevBuf raw, t4, f4, tb, fb, m0, m1;
-  int rc = 0;
-  if (raw.ensure(n * 6) || t4.ensure(n * 8) || f4.ensure(n * 8) || tb.ensure(n * 8) || fb.ensure(n * 8) || m0.ensure(n) ||
-      m1.ensure(n)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(raw.p, template_bgr, n * 6, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, raw.as<uint16_t>(), t4.as<ushort4>(), n);
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipMemcpy(raw.p, frame_bgr, n * 6, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, raw.as<uint16_t>(), f4.as<ushort4>(), n);
-    const ushort4 *tp = t4.as<ushort4>(), *fp = f4.as<ushort4>();
-    if (blur_radius > 0) {
-      hipLaunchKernelGGL(k_gauss_u16, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, t4.as<ushort4>(), tb.as<ushort4>(), w, h, blur_radius);
-      hipLaunchKernelGGL(k_gauss_u16, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, f4.as<ushort4>(), fb.as<ushort4>(), w, h, blur_radius);
-      tp = tb.as<ushort4>();
-      fp = fb.as<ushort4>();
-    }
-    hipLaunchKernelGGL(k_fg_threshold, dim3(flat_grid(n)), dim3(256), 0, c->stream, tp, fp, n, threshold, m0.as<uint8_t>());
-    const uint8_t* res = m0.as<uint8_t>();
-    if (morph_closing_size > 0) {
-      hipLaunchKernelGGL(k_morph_rect, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, m0.as<uint8_t>(), m1.as<uint8_t>(), w, h, morph_closing_size, 1);
-      hipLaunchKernelGGL(k_morph_rect, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, m1.as<uint8_t>(), m0.as<uint8_t>(), w, h, morph_closing_size, 0);
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(mask01, res, n, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_generate_foreground_mask: %s", hipGetErrorString(hipGetLastError()));
-    }
+  ALLOC(c, t4, n * 8);
+  ALLOC(c, f4, n * 8);
+  ALLOC(c, m0, n);
+  TRY(upload_sync(c, raw, template_bgr, n * 6));
+  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, raw.as<uint16_t>(), t4.as<ushort4>(), n);
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // `raw` is overwritten by the frame
+  TRY(upload_sync(c, raw, frame_bgr, n * 6));
+  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, raw.as<uint16_t>(), f4.as<ushort4>(), n);
+  const ushort4 *tp = t4.as<ushort4>(), *fp = f4.as<ushort4>();
+  if (blur_radius > 0) {
+    ALLOC(c, tb, n * 8);
+    ALLOC(c, fb, n * 8);
+    hipLaunchKernelGGL(k_gauss_u16, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, t4.as<ushort4>(), tb.as<ushort4>(), w, h, blur_radius);
+    hipLaunchKernelGGL(k_gauss_u16, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, f4.as<ushort4>(), fb.as<ushort4>(), w, h, blur_radius);
+    tp = tb.as<ushort4>();
+    fp = fb.as<ushort4>();
   }
-  for (DevBuf* b : {&raw, &t4, &f4, &tb, &fb, &m0, &m1}) {
-    b->release();
+  hipLaunchKernelGGL(k_fg_threshold, dim3(flat_grid(n)), dim3(256), 0, c->stream, tp, fp, n, threshold, m0.as<uint8_t>());
+  if (morph_closing_size > 0) {
+    ALLOC(c, m1, n);
+    hipLaunchKernelGGL(k_morph_rect, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, m0.as<uint8_t>(), m1.as<uint8_t>(), w, h, morph_closing_size, 1);
+    hipLaunchKernelGGL(k_morph_rect, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, m1.as<uint8_t>(), m0.as<uint8_t>(), w, h, morph_closing_size, 0);
   }
-  return rc;
+  return download_sync(c, mask01, m0.p, n);
 }
 
 // ---- sibling binaries' kernels, host-pointer convenience forms ----
@@ -2243,22 +2164,12 @@ int derp_layer_disparities(derp_ctx* c, const float* foreground, const float* ba
   }
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf f, b, o;
-  int rc = 0;
-  if (f.ensure(n * 4) || b.ensure(n * 4) || o.ensure(n)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(f.p, foreground, n * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(b.p, background, n * 4, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_layer_disparities, dim3(flat_grid(n)), dim3(256), 0, c->stream, f.as<float>(), b.as<float>(), n,
-                       o.as<uint8_t>());
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, o.p, n, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_layer_disparities: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
-  for (DevBuf* x : {&f, &b, &o}) {
-    x->release();
-  }
-  return rc;
+  TRY(upload_sync(c, f, foreground, n * 4));
+  TRY(upload_sync(c, b, background, n * 4));
+  ALLOC(c, o, n);
+  hipLaunchKernelGGL(k_layer_disparities, dim3(flat_grid(n)), dim3(256), 0, c->stream, f.as<float>(), b.as<float>(), n,
+                     o.as<uint8_t>());
+  return download_sync(c, out, o.p, n);
 }
 // ---- rephotography score (RephotographyUtil.h:38-116, ComputeRephotographyErrors.cpp:69-189) ----
 int derp_ssim(derp_ctx* c, const float* x_bgr, const float* y_bgr, int w, int h, int blur_radius, float alpha,
@@ -2291,40 +2202,28 @@ int derp_ssim(derp_ctx* c, const float* x_bgr, const float* y_bgr, int w, int h,
   }
   const size_t n3 = (size_t)w * h * 3, bytes = n3 * 4;
   DevBuf x, y, muX, muY, a, b, cc, tmp, s2x, s2y, sxy;
-  int rc = 0;
-  bool oom = false;
-  for (DevBuf* buf : {&x, &y, &muX, &muY, &a, &b, &cc, &tmp, &s2x, &s2y, &sxy}) {
-    oom = oom || buf->ensure(bytes);
+  TRY(upload_sync(c, x, x_bgr, bytes));
+  TRY(upload_sync(c, y, y_bgr, bytes));
+  for (DevBuf* buf : {&muX, &muY, &a, &b, &cc, &tmp, &s2x, &s2y, &sxy}) {
+    ALLOC(c, *buf, bytes);
   }
-  if (oom) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(x.p, x_bgr, bytes, hipMemcpyHostToDevice);
-    (void)hipMemcpy(y.p, y_bgr, bytes, hipMemcpyHostToDevice);
-    const dim3 grid = grid2d(w * 3, h, 1, kBlk2d);
-    auto blur = [&](const DevBuf& in, DevBuf& out) {
-      hipLaunchKernelGGL(k_gauss_f32c3, grid, kBlk2d, 0, c->stream, in.as<float>(), tmp.as<float>(), w, h, blur_radius, coef, 0);
-      hipLaunchKernelGGL(k_gauss_f32c3, grid, kBlk2d, 0, c->stream, tmp.as<float>(), out.as<float>(), w, h, blur_radius, coef, 1);
-    };
-    blur(x, muX);
-    blur(y, muY);
-    hipLaunchKernelGGL(k_ssim_moments, dim3(flat_grid(n3)), dim3(256), 0, c->stream, x.as<float>(), y.as<float>(),
-                       muX.as<float>(), muY.as<float>(), a.as<float>(), b.as<float>(), cc.as<float>(), n3);
-    blur(a, s2x);
-    blur(b, s2y);
-    blur(cc, sxy);
-    // the score overwrites `a`
-    hipLaunchKernelGGL(k_ssim_score, dim3(flat_grid(n3)), dim3(256), 0, c->stream, muX.as<float>(), muY.as<float>(),
-                       s2x.as<float>(), s2y.as<float>(), sxy.as<float>(), alpha != 0.0f, beta != 0.0f, gamma != 0.0f,
-                       a.as<float>(), n3);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(score_bgr, a.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_ssim: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
-  for (DevBuf* buf : {&x, &y, &muX, &muY, &a, &b, &cc, &tmp, &s2x, &s2y, &sxy}) {
-    buf->release();
-  }
-  return rc;
+  const dim3 grid = grid2d(w * 3, h, 1, kBlk2d);
+  auto blur = [&](const DevBuf& in, DevBuf& out) {
+    hipLaunchKernelGGL(k_gauss_f32c3, grid, kBlk2d, 0, c->stream, in.as<float>(), tmp.as<float>(), w, h, blur_radius, coef, 0);
+    hipLaunchKernelGGL(k_gauss_f32c3, grid, kBlk2d, 0, c->stream, tmp.as<float>(), out.as<float>(), w, h, blur_radius, coef, 1);
+  };
+  blur(x, muX);
+  blur(y, muY);
+  hipLaunchKernelGGL(k_ssim_moments, dim3(flat_grid(n3)), dim3(256), 0, c->stream, x.as<float>(), y.as<float>(),
+                     muX.as<float>(), muY.as<float>(), a.as<float>(), b.as<float>(), cc.as<float>(), n3);
+  blur(a, s2x);
+  blur(b, s2y);
+  blur(cc, sxy);
+  // the score overwrites `a`
+  hipLaunchKernelGGL(k_ssim_score, dim3(flat_grid(n3)), dim3(256), 0, c->stream, muX.as<float>(), muY.as<float>(),
+                     s2x.as<float>(), s2y.as<float>(), sxy.as<float>(), alpha != 0.0f, beta != 0.0f, gamma != 0.0f,
+                     a.as<float>(), n3);
+  return download_sync(c, score_bgr, a.p, bytes);
 }
 
 int derp_average_score(const float* score_bgr, const uint8_t* mask, int w, int h, double* avg_bgr3) {
@@ -2382,23 +2281,14 @@ int derp_rephotograph_render(derp_ctx* c, int target, float* out_bgra) {
   const int w = c->rephotoW, h = c->rephotoH;
   const size_t n = (size_t)w * h;
   DevBuf key, out;
-  int rc = 0;
-  if (key.ensure(n * 8) || out.ensure(n * 16)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemsetAsync(key.p, 0xff, n * 8, c->stream);
-    hipLaunchKernelGGL(k_rephoto_splat, grid2d(w, h, c->S, kBlk2d), kBlk2d, 0, c->stream, c->camsSrc.as<Cam>(), target,
-                       c->rephotoDisp.as<float>(), w, h, key.as<unsigned long long>());
-    hipLaunchKernelGGL(k_rephoto_resolve, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsSrc.as<Cam>(), target,
-                       c->rephotoColor.as<uint16_t>(), key.as<unsigned long long>(), w, h, out.as<float4>());
-    if (hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(out_bgra, out.p, n * 16, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_rephotograph_render: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
-  key.release();
-  out.release();
-  return rc;
+  ALLOC(c, key, n * 8);
+  ALLOC(c, out, n * 16);
+  HIPCHK(c, hipMemsetAsync(key.p, 0xff, n * 8, c->stream));
+  hipLaunchKernelGGL(k_rephoto_splat, grid2d(w, h, c->S, kBlk2d), kBlk2d, 0, c->stream, c->camsSrc.as<Cam>(), target,
+                     c->rephotoDisp.as<float>(), w, h, key.as<unsigned long long>());
+  hipLaunchKernelGGL(k_rephoto_resolve, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsSrc.as<Cam>(), target,
+                     c->rephotoColor.as<uint16_t>(), key.as<unsigned long long>(), w, h, out.as<float4>());
+  return download_sync(c, out_bgra, out.p, n * 16);
 }
 
 int derp_rephotograph(derp_ctx* c, int target, const uint16_t* const* colors, const float* const* disparities, int w,
@@ -2509,7 +2399,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t n = npx(c, c->cur);
-  HIPCHK(c, hipMemcpy(out, c->mismatchMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, c->w.mismatchMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
   return 0;
 }
 int derp_fov_mask(derp_ctx* c, int d, int w, int h, uint8_t* out) {
@@ -2518,18 +2408,10 @@ int derp_fov_mask(derp_ctx* c, int d, int w, int h, uint8_t* out) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf m;
-  if (m.ensure((size_t)w * h)) {
-    return fail(c, "out of device memory");
-  }
+  ALLOC(c, m, (size_t)w * h);
   hipLaunchKernelGGL(k_fov_mask, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>() + d, w, h,
                      m.as<uint8_t>());
-  int rc = 0;
-  if (hipStreamSynchronize(c->stream) != hipSuccess ||
-      hipMemcpy(out, m.p, (size_t)w * h, hipMemcpyDeviceToHost) != hipSuccess) {
-    rc = fail(c, "HIP error in derp_fov_mask: %s", hipGetErrorString(hipGetLastError()));
-  }
-  m.release();
-  return rc;
+  return download_sync(c, out, m.p, (size_t)w * h);
 }
 
 int derp_upsample_disparity(derp_ctx* c, int d, const float* disp, int w, int h, const float* bg_disp_up,
@@ -2540,64 +2422,35 @@ int derp_upsample_disparity(derp_ctx* c, int d, const float* disp, int w, int h,
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h, nu = (size_t)w_up * h_up;
-  DevBuf in, res, m, mu, bg, fov, fovu;
-  int rc = 0;
-  auto cleanup = [&]() {
-    for (DevBuf* b : {&in, &res, &m, &mu, &bg, &fov, &fovu}) {
-      b->release();
-    }
-  };
-  do {
-    if (in.ensure(n * 4) || res.ensure(nu * 4)) {
-      rc = fail(c, "out of device memory");
-      break;
-    }
-    (void)hipMemcpy(in.p, disp, n * 4, hipMemcpyHostToDevice);
-    if (!use_fg) {
-      rc = upsample_lanczos_dev(c, in.as<float>(), w, h, res.as<float>(), w_up, h_up, 1, n, nu);
-    } else {
-      if (!bg_disp_up || !fg_mask || !fg_mask_up) {
-        rc = fail(c, "foreground-mask upsample needs bg_disp_up, fg_mask and fg_mask_up");
-        break;
-      }
-      if (m.ensure(n) || mu.ensure(nu) || bg.ensure(nu * 4) || fov.ensure(n) || fovu.ensure(nu)) {
-        rc = fail(c, "out of device memory");
-        break;
-      }
-      (void)hipMemcpy(m.p, fg_mask, n, hipMemcpyHostToDevice);
-      (void)hipMemcpy(mu.p, fg_mask_up, nu, hipMemcpyHostToDevice);
-      (void)hipMemcpy(bg.p, bg_disp_up, nu * 4, hipMemcpyHostToDevice);
-      const int zero = 0;
-      DevBuf idx;
-      if (idx.ensure(sizeof(int))) {
-        rc = fail(c, "out of device memory");
-        break;
-      }
-      (void)hipMemcpy(idx.p, &zero, sizeof(int), hipMemcpyHostToDevice);
-      // fov masks of camera d at both sizes, AND-ed with the fg masks (UpsampleDisparityLib.cpp:163-179)
-      hipLaunchKernelGGL(k_fov_mask, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>() + d, w, h,
-                         fov.as<uint8_t>());
-      hipLaunchKernelGGL(k_fov_mask, grid2d(w_up, h_up, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>() + d,
-                         w_up, h_up, fovu.as<uint8_t>());
-      hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), 1), dim3(256), 0, c->stream, fov.as<uint8_t>(),
-                         m.as<uint8_t>(), idx.as<int>(), 0, n, fov.as<uint8_t>());
-      hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(nu), 1), dim3(256), 0, c->stream, fovu.as<uint8_t>(),
-                         mu.as<uint8_t>(), idx.as<int>(), 0, nu, fovu.as<uint8_t>());
-      rc = upsample_masked_dev(c, in.as<float>(), fov.as<uint8_t>(), w, h, fovu.as<uint8_t>(), bg.as<float>(),
-                               res.as<float>(), w_up, h_up);
-      (void)hipStreamSynchronize(c->stream);
-      idx.release();
-    }
-    if (rc) {
-      break;
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess ||
-        hipMemcpy(out, res.p, nu * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_upsample_disparity");
-    }
-  } while (0);
-  cleanup();
-  return rc;
+  DevBuf in, res, m, mu, bg, fov, fovu, idx;
+  TRY(upload_sync(c, in, disp, n * 4));
+  ALLOC(c, res, nu * 4);
+  if (!use_fg) {
+    TRY(upsample_lanczos_dev(c, in.as<float>(), w, h, res.as<float>(), w_up, h_up, 1, n, nu));
+    return download_sync(c, out, res.p, nu * 4);
+  }
+  if (!bg_disp_up || !fg_mask || !fg_mask_up) {
+    return fail(c, "foreground-mask upsample needs bg_disp_up, fg_mask and fg_mask_up");
+  }
+  const int zero = 0;
+  TRY(upload_sync(c, m, fg_mask, n));
+  TRY(upload_sync(c, mu, fg_mask_up, nu));
+  TRY(upload_sync(c, bg, bg_disp_up, nu * 4));
+  TRY(upload_sync(c, idx, &zero, sizeof(int)));
+  ALLOC(c, fov, n);
+  ALLOC(c, fovu, nu);
+  // fov masks of camera d at both sizes, AND-ed with the fg masks (UpsampleDisparityLib.cpp:163-179)
+  hipLaunchKernelGGL(k_fov_mask, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>() + d, w, h,
+                     fov.as<uint8_t>());
+  hipLaunchKernelGGL(k_fov_mask, grid2d(w_up, h_up, 1, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>() + d, w_up,
+                     h_up, fovu.as<uint8_t>());
+  hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), 1), dim3(256), 0, c->stream, fov.as<uint8_t>(), m.as<uint8_t>(),
+                     idx.as<int>(), 0, n, fov.as<uint8_t>());
+  hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(nu), 1), dim3(256), 0, c->stream, fovu.as<uint8_t>(), mu.as<uint8_t>(),
+                     idx.as<int>(), 0, nu, fovu.as<uint8_t>());
+  TRY(upsample_masked_dev(c, in.as<float>(), fov.as<uint8_t>(), w, h, fovu.as<uint8_t>(), bg.as<float>(), res.as<float>(),
+                          w_up, h_up));
+  return download_sync(c, out, res.p, nu * 4);
 }
 
 int derp_joint_bilateral_u16(derp_ctx* c, const float* image, const uint16_t* guide, const uint8_t* mask, int w, int h,
@@ -2608,25 +2461,16 @@ int derp_joint_bilateral_u16(derp_ctx* c, const float* image, const uint16_t* gu
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
   DevBuf im, g3, g4, m, res;
-  int rc = 0;
-  if (im.ensure(n * 4) || g3.ensure(n * 6) || g4.ensure(n * 8) || m.ensure(n) || res.ensure(n * 4)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(im.p, image, n * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(g3.p, guide, n * 6, hipMemcpyHostToDevice);
-    (void)hipMemcpy(m.p, mask, n, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, g3.as<uint16_t>(), g4.as<ushort4>(), n);
-    hipLaunchKernelGGL(k_joint_bilateral<true>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
-                       bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g4.as<ushort4>(),
-                       m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, res.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_joint_bilateral_u16: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
-  for (DevBuf* b : {&im, &g3, &g4, &m, &res}) {
-    b->release();
-  }
-  return rc;
+  TRY(upload_sync(c, im, image, n * 4));
+  TRY(upload_sync(c, g3, guide, n * 6));
+  TRY(upload_sync(c, m, mask, n));
+  ALLOC(c, g4, n * 8);
+  ALLOC(c, res, n * 4);
+  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, g3.as<uint16_t>(), g4.as<ushort4>(), n);
+  hipLaunchKernelGGL(k_joint_bilateral<true>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
+                     bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g4.as<ushort4>(),
+                     m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
+  return download_sync(c, out, res.p, n * 4);
 }
 
 int derp_joint_bilateral_f32(derp_ctx* c, const float* image, const float* guide, const uint8_t* mask, int w, int h,
@@ -2637,24 +2481,14 @@ int derp_joint_bilateral_f32(derp_ctx* c, const float* image, const float* guide
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
   DevBuf im, g, m, res;
-  int rc = 0;
-  if (im.ensure(n * 4) || g.ensure(n * 12) || m.ensure(n) || res.ensure(n * 4)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(im.p, image, n * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(g.p, guide, n * 12, hipMemcpyHostToDevice);
-    (void)hipMemcpy(m.p, mask, n, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_joint_bilateral<false>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
-                       bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g.as<float>(),
-                       m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, res.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_joint_bilateral_f32: %s", hipGetErrorString(hipGetLastError()));
-    }
-  }
-  for (DevBuf* b : {&im, &g, &m, &res}) {
-    b->release();
-  }
-  return rc;
+  TRY(upload_sync(c, im, image, n * 4));
+  TRY(upload_sync(c, g, guide, n * 12));
+  TRY(upload_sync(c, m, mask, n));
+  ALLOC(c, res, n * 4);
+  hipLaunchKernelGGL(k_joint_bilateral<false>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
+                     bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g.as<float>(),
+                     m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
+  return download_sync(c, out, res.p, n * 4);
 }
 
 int derp_masked_median(derp_ctx* c, const float* image, const float* background, const uint8_t* mask, int w, int h,
@@ -2665,26 +2499,16 @@ int derp_masked_median(derp_ctx* c, const float* image, const float* background,
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
   DevBuf im, bg, m, res;
-  int rc = 0;
-  if (im.ensure(n * 4) || (background && bg.ensure(n * 4)) || m.ensure(n) || res.ensure(n * 4)) {
-    rc = fail(c, "out of device memory");
-  } else {
-    (void)hipMemcpy(im.p, image, n * 4, hipMemcpyHostToDevice);
-    if (background) {
-      (void)hipMemcpy(bg.p, background, n * 4, hipMemcpyHostToDevice);
-    }
-    (void)hipMemcpy(m.p, mask, n, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_masked_median, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, im.as<float>(),
-                       background ? bg.as<float>() : (const float*)nullptr, m.as<uint8_t>(), w, h, radius,
-                       res.as<float>(), n, (const uint8_t*)nullptr);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, res.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_masked_median: %s", hipGetErrorString(hipGetLastError()));
-    }
+  TRY(upload_sync(c, im, image, n * 4));
+  if (background) {
+    TRY(upload_sync(c, bg, background, n * 4));
   }
-  for (DevBuf* b : {&im, &bg, &m, &res}) {
-    b->release();
-  }
-  return rc;
+  TRY(upload_sync(c, m, mask, n));
+  ALLOC(c, res, n * 4);
+  hipLaunchKernelGGL(k_masked_median, grid2d(w, h, 1, kBlk2d), kBlk2d, 0, c->stream, im.as<float>(),
+                     background ? bg.as<float>() : (const float*)nullptr, m.as<uint8_t>(), w, h, radius,
+                     res.as<float>(), n, (const uint8_t*)nullptr);
+  return download_sync(c, out, res.p, n * 4);
 }
 
 int derp_temporal_filter_dev(derp_ctx* c, const void* const* guides, const float* const* disps,
@@ -2708,53 +2532,25 @@ int derp_temporal_filter(derp_ctx* c, const uint16_t* const* guides, const float
   const size_t n = (size_t)w * h;
   std::vector<DevBuf> g4(n_frames), im(n_frames), m(n_frames);
   DevBuf g3, res;
-  int rc = 0;
-  std::vector<const void*> gpv(n_frames);
-  std::vector<const float*> ipv(n_frames);
-  std::vector<const uint8_t*> mpv(n_frames);
-  const void** gp = gpv.data();
-  const float** ip = ipv.data();
-  const uint8_t** mp = mpv.data();
-  do {
-    if (g3.ensure(n * 6) || res.ensure(n * 4)) {
-      rc = fail(c, "out of device memory");
-      break;
-    }
-    for (int t = 0; t < n_frames && !rc; ++t) {
-      if (g4[t].ensure(n * 8) || im[t].ensure(n * 4) || m[t].ensure(n)) {
-        rc = fail(c, "out of device memory");
-        break;
-      }
-      (void)hipMemcpy(g3.p, guides[t], n * 6, hipMemcpyHostToDevice);
-      hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, g3.as<uint16_t>(),
-                         g4[t].as<ushort4>(), n);
-      (void)hipStreamSynchronize(c->stream);
-      (void)hipMemcpy(im[t].p, disps[t], n * 4, hipMemcpyHostToDevice);
-      (void)hipMemcpy(m[t].p, masks[t], n, hipMemcpyHostToDevice);
-      gp[t] = g4[t].p;
-      ip[t] = im[t].as<float>();
-      mp[t] = m[t].as<uint8_t>();
-    }
-    if (rc) {
-      break;
-    }
-    rc = derp_temporal_filter_dev(c, gp, ip, mp, n_frames, w, h, frame_offset, sigma, space_radius, w0, w1, w2,
-                                  res.as<float>());
-    if (rc) {
-      break;
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, res.p, n * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error in derp_temporal_filter: %s", hipGetErrorString(hipGetLastError()));
-    }
-  } while (0);
-  for (auto* v : {&g4, &im, &m}) {
-    for (auto& b : *v) {
-      b.release();
-    }
+  std::vector<const void*> gp(n_frames);
+  std::vector<const float*> ip(n_frames);
+  std::vector<const uint8_t*> mp(n_frames);
+  for (int t = 0; t < n_frames; ++t) {
+    ALLOC(c, g4[t], n * 8);
+    TRY(upload_sync(c, g3, guides[t], n * 6));
+    hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, g3.as<uint16_t>(),
+                       g4[t].as<ushort4>(), n);
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // `g3` is overwritten by the next frame
+    TRY(upload_sync(c, im[t], disps[t], n * 4));
+    TRY(upload_sync(c, m[t], masks[t], n));
+    gp[t] = g4[t].p;
+    ip[t] = im[t].as<float>();
+    mp[t] = m[t].as<uint8_t>();
   }
-  g3.release();
-  res.release();
-  return rc;
+  ALLOC(c, res, n * 4);
+  TRY(derp_temporal_filter_dev(c, gp.data(), ip.data(), mp.data(), n_frames, w, h, frame_offset, sigma, space_radius, w0,
+                               w1, w2, res.as<float>()));
+  return download_sync(c, out, res.p, n * 4);
 }
 
 int derp_dev_disparity(derp_ctx* c, int level, int d, float** ptr, size_t* bytes) {
@@ -2763,7 +2559,7 @@ int derp_dev_disparity(derp_ctx* c, int level, int d, float** ptr, size_t* bytes
     return fail(c, "bad destination index / null output");
   }
   const size_t n = npx(c, level);
-  *ptr = c->pyrDisp[level].as<float>() + (size_t)d * n;
+  *ptr = c->frame().disp[level].as<float>() + (size_t)d * n;
   *bytes = n * sizeof(float);
   return 0;
 }
@@ -2773,7 +2569,7 @@ int derp_dev_color(derp_ctx* c, int level, int s, void** ptr, size_t* bytes) {
     return fail(c, "bad source index / null output");
   }
   const size_t n = npx(c, level);
-  *ptr = c->pyrColor[level].as<ushort4>() + (size_t)s * n;
+  *ptr = c->frame().color[level].as<ushort4>() + (size_t)s * n;
   *bytes = n * sizeof(ushort4);
   return 0;
 }
@@ -2792,7 +2588,7 @@ int derp_dev_mask(derp_ctx* c, int level, int d, uint8_t** ptr, size_t* bytes) {
                      c->devMask.as<uint8_t>());
   KCHECK(c);
   hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), c->D), dim3(256), 0, c->stream, c->devMask.as<uint8_t>(),
-                     c->pyrFg[level].as<uint8_t>(), c->dst2src.as<int>(), 0, n, c->devMask.as<uint8_t>());
+                     c->frame().fg[level].as<uint8_t>(), c->dst2src.as<int>(), 0, n, c->devMask.as<uint8_t>());
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *ptr = c->devMask.as<uint8_t>() + (size_t)d * n;
@@ -2989,8 +2785,7 @@ int derp_render_upload(derp_ctx* c, const float* const* colors_bgra, const int* 
   }
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  smr_free(c);
-  c->smr = new SmrState;
+  c->smr = std::make_unique<SmrState>();
   SmrState& S = *c->smr;
   S.cams.resize(c->S);
   S.haveColor = colors_bgra != nullptr;

@@ -185,7 +185,7 @@ __device__ __forceinline__ v2f bg_of(unsigned u) {
 
 // The destination colours a wave's 8x8 pixel tile compares against — the 3x3 patches of its 64 pixels overlap, so the
 // wave keeps ONE 10x10 window of its destination camera's colour (as floats) in LDS instead of 27 floats per lane in
-// registers (round 6: those 27 + the 18 parked per-offset sums were what pinned the cost kernels at 164-167 VGPRs, an odd
+// registers (round 6: those 27 + the 18 held per-offset sums were what pinned the cost kernels at 164-167 VGPRs, an odd
 // three waves per SIMD). (B, G) and R live in separate planes: a (B, G) pair arrives as one aligned register pair
 // (ds_read_b64), and R of the offsets dy = -1 / +1 as one pair too (ds_read2_b32, two rows of the R plane).
 static constexpr int kWinW = 10, kWinTexels = kWinW * kWinW;
@@ -430,7 +430,7 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   // --- the 4x4 texel block arithmetic shared by the two block-shaped paths below. The block is streamed by COLUMNS
   // (round 6): offset column ix needs texel columns ix and ix + 1 only, and computeSSD's loop runs dx outer / dy inner
   // (DerpUtil.cpp:135-136), so the nine per-offset terms are added to the two sums the moment they exist, in the
-  // reference's order — streamed by rows (rounds 2-5) the terms came out dy-major and 18 of them were parked in
+  // reference's order — streamed by rows (rounds 2-5) the terms came out dy-major and 18 of them were held in
   // registers until the end. Each operation is the same IEEE operation, in the same order, as the scalar expression it
   // replaces; the destination patch comes from the wave's LDS window (PixCtx).
   float first = 0.f, second = 0.f;
@@ -706,7 +706,7 @@ __device__ __forceinline__ unsigned behind_sources(const LevelView& V, int d, si
 // kCullMinDepth; they are skipped without their cone test. 0 = test every source.
 // RANDOM: the random-proposal shape of computeSSD (ssd_arith) and of `sees` (cost_sees_lean).
 // RELOAD_RAY (ping-pong, random proposals): the pixel's ray direction is read from the rayDir table at every call (pixel
-// index `pix`) instead of living in six registers across the candidate loop — where the allocator parked it in scratch
+// index `pix`) instead of living in six registers across the candidate loop — where the allocator spilled it to scratch
 // (one store per pixel, one load per candidate: 2.4 GB of scratch writes per level-0 launch at config 2, round 4). The
 // opaque copy of the index keeps the loads inside the loop.
 // developer build (-DDERP_PHASE_TIMERS=1|2): wave cycles (s_memtime) spent in computeCost's phases, reported through the

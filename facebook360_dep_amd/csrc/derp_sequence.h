@@ -201,19 +201,6 @@ int edge_index(const derp_seq* q, int frame) {
   return it != q->edge.end() && *it == frame ? (int)(it - q->edge.begin()) : -1;
 }
 
-// pyramid buffers of a frame slot whether it is selected or parked
-struct SlotView {
-  std::vector<DevBuf>*color, *fg, *disp;
-  std::vector<char>* haveDisp;
-};
-SlotView slot_view(derp_ctx* c, int slot) {
-  if (slot == c->curSlot) {
-    return {&c->pyrColor, &c->pyrFg, &c->pyrDisp, &c->haveDisp};
-  }
-  derp_ctx::FrameSlot& fs = c->parked[slot];
-  return {&fs.pyrColor, &fs.pyrFg, &fs.pyrDisp, &fs.haveDisp};
-}
-
 // kind: 0 colour pyramid level (ushort4 [S][n]), 1 fg mask (u8 [S][n]), 2 level disparity (f32 [D][n])
 int seq_buffer(derp_seq* q, int frame, int level, int kind, void** ptr, size_t* bytes) {
   derp_ctx* c = q->c;
@@ -237,8 +224,8 @@ int seq_buffer(derp_seq* q, int frame, int level, int kind, void** ptr, size_t* 
       return fail(c, "edge buffer of frame %d level %d kind %d was not allocated", frame, level, kind);
     }
   } else if (oi >= 0) {
-    SlotView v = slot_view(c, oi);
-    b = kind == 0 ? &(*v.color)[level] : kind == 1 ? &(*v.fg)[level] : &(*v.disp)[level];
+    FramePyramid& f = c->frames[oi];
+    b = kind == 0 ? &f.color[level] : kind == 1 ? &f.fg[level] : &f.disp[level];
   } else {
     const int hi = halo_index(q, frame);
     if (hi < 0) {
@@ -483,7 +470,9 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
   if (last < first || world < 1 || rank < 0 || rank >= world) {
     return fail(c, "bad sequence geometry: frames %d..%d, rank %d of %d", first, last, rank, world);
   }
-  derp_seq* q = new derp_seq;
+  // until success: an early return tears down what exists so far
+  std::unique_ptr<derp_seq, void (*)(derp_seq*)> owner(new derp_seq, derp_seq_destroy);
+  derp_seq* q = owner.get();
   q->c = c;
   q->first = first;
   q->last = last;
@@ -494,12 +483,8 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
   } else {
     derp_seq_options_default(&q->opt);
   }
-  auto bail = [&](int rc) {
-    derp_seq_destroy(q);
-    return rc;
-  };
   if (q->opt.time_radius < 0) {
-    return bail(fail(c, "time_radius %d is negative", q->opt.time_radius));
+    return fail(c, "time_radius %d is negative", q->opt.time_radius);
   }
   if (!q->opt.do_temporal_filter) {
     q->opt.time_radius = 0;  // no window, no halo, no exchange: replicas
@@ -516,22 +501,23 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
     }
   }
   if (hipSetDevice(c->device) != hipSuccess) {
-    return bail(fail(c, "hipSetDevice failed"));
+    return fail(c, "hipSetDevice failed");
   }
   const int nOwned = (int)q->owned.size();
   q->streaming = q->opt.resident_frames > 0 && q->opt.resident_frames < nOwned;
   q->nSlots = q->streaming ? q->opt.resident_frames : std::max(1, nOwned);
   if (q->streaming && q->opt.do_temporal_filter && q->nSlots < 2 * q->opt.time_radius + 1) {
-    return bail(fail(c, "resident_frames %d is smaller than the temporal window (2 * time_radius + 1 = %d frames)",
-                     q->nSlots, 2 * q->opt.time_radius + 1));
+    return fail(c, "resident_frames %d is smaller than the temporal window (2 * time_radius + 1 = %d frames)",
+                q->nSlots, 2 * q->opt.time_radius + 1);
   }
-  if (derp_set_frame_slots(c, q->nSlots)) {
-    return bail(1);
-  }
+  TRY(derp_set_frame_slots(c, q->nSlots));
   const int nl = c->numLevels;
-  q->haloColor.assign(q->halo.size(), std::vector<DevBuf>(nl));
-  q->haloFg.assign(q->halo.size(), std::vector<DevBuf>(nl));
-  q->haloDisp.assign(q->halo.size(), std::vector<DevBuf>(nl));
+  for (auto* vv : {&q->haloColor, &q->haloFg, &q->haloDisp}) {
+    vv->resize(q->halo.size());
+    for (auto& v : *vv) {
+      v.resize(nl);
+    }
+  }
   size_t nmax = 0;
   for (int l = 0; l < nl; ++l) {
     const size_t n = npx(c, l);
@@ -542,7 +528,7 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
     for (size_t h = 0; h < q->halo.size(); ++h) {
       if (q->haloColor[h][l].ensure(n * c->S * sizeof(ushort4)) || q->haloDisp[h][l].ensure(n * c->D * sizeof(float)) ||
           (q->opt.use_foreground_masks && q->haloFg[h][l].ensure(n * c->S))) {
-        return bail(fail(c, "out of device memory allocating the temporal halo (frame %d, level %d)", q->halo[h], l));
+        return fail(c, "out of device memory allocating the temporal halo (frame %d, level %d)", q->halo[h], l);
       }
     }
   }
@@ -552,17 +538,17 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
   if (hipStreamCreateWithFlags(&q->xStream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&q->computedEv, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&q->exchangedEv, hipEventDisableTiming) != hipSuccess) {
-    return bail(fail(c, "hipStreamCreate / hipEventCreate failed"));
+    return fail(c, "hipStreamCreate / hipEventCreate failed");
   }
   q->filteredEv.assign(q->streaming ? 0 : q->owned.size(), nullptr);
   for (auto& e : q->filteredEv) {
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-      return bail(fail(c, "hipEventCreate failed"));
+      return fail(c, "hipEventCreate failed");
     }
   }
   for (auto& b : q->filtered) {
     if (b.ensure(nmax * c->D * sizeof(float))) {
-      return bail(fail(c, "out of device memory allocating the filtered level"));
+      return fail(c, "out of device memory allocating the filtered level");
     }
   }
   if (q->streaming) {
@@ -574,13 +560,13 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
     for (int k = 0; k < nOwned; ++k) {
       if (q->opt.do_temporal_filter && hipHostMalloc((void**)&q->hostRaw[k], nmax * c->D * sizeof(float), hipHostMallocDefault) != hipSuccess) {
         q->hostRaw[k] = nullptr;
-        return bail(fail(c, "out of page-locked host memory for the raw level of frame %d", q->owned[k]));
+        return fail(c, "out of page-locked host memory for the raw level of frame %d", q->owned[k]);
       }
       for (int l = 0; l < nl; ++l) {
         const size_t n = npx(c, l);
         if (n && hipHostMalloc((void**)&q->hostDisp[k][l], n * c->D * sizeof(float), hipHostMallocDefault) != hipSuccess) {
           q->hostDisp[k][l] = nullptr;
-          return bail(fail(c, "out of page-locked host memory for the results of frame %d", q->owned[k]));
+          return fail(c, "out of page-locked host memory for the results of frame %d", q->owned[k]);
         }
       }
     }
@@ -589,27 +575,31 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
         q->edge.push_back(tr.frame);
       }
     }
-    q->edgeColor.assign(q->edge.size(), std::vector<DevBuf>(nl));
-    q->edgeFg.assign(q->edge.size(), std::vector<DevBuf>(nl));
+    for (auto* vv : {&q->edgeColor, &q->edgeFg}) {
+      vv->resize(q->edge.size());
+      for (auto& v : *vv) {
+        v.resize(nl);
+      }
+    }
     q->edgeRaw.resize(q->edge.size());
     for (size_t e = 0; e < q->edge.size(); ++e) {
       if (q->edgeRaw[e].ensure(nmax * c->D * sizeof(float))) {
-        return bail(fail(c, "out of device memory allocating the edge frames"));
+        return fail(c, "out of device memory allocating the edge frames");
       }
       for (int l = 0; l < nl; ++l) {
         const size_t n = npx(c, l);
         if (n && (q->edgeColor[e][l].ensure(n * c->S * sizeof(ushort4)) ||
                   (q->opt.use_foreground_masks && q->edgeFg[e][l].ensure(n * c->S)))) {
-          return bail(fail(c, "out of device memory allocating the edge frames"));
+          return fail(c, "out of device memory allocating the edge frames");
         }
       }
     }
   }
   if (q->fov.ensure(nmax * c->D) ||
       (q->opt.use_foreground_masks && q->winMask.ensure((size_t)(2 * q->opt.time_radius + 1) * nmax * c->D))) {
-    return bail(fail(c, "out of device memory allocating the temporal masks"));
+    return fail(c, "out of device memory allocating the temporal masks");
   }
-  *out = q;
+  *out = owner.release();  // (the unique_ptr's: the caller owns the sequence now)
   return 0;
 }
 
@@ -625,16 +615,6 @@ void derp_seq_destroy(derp_seq* q) {
   if (q->comm) {
     (void)rccl_api()->CommDestroy(q->comm);
   }
-  for (auto* vv : {&q->haloColor, &q->haloFg, &q->haloDisp}) {
-    for (auto& v : *vv) {
-      for (auto& b : v) {
-        b.release();
-      }
-    }
-  }
-  for (auto& b : q->filtered) {
-    b.release();
-  }
   for (auto& e : q->filteredEv) {
     if (e) {
       (void)hipEventDestroy(e);
@@ -649,8 +629,6 @@ void derp_seq_destroy(derp_seq* q) {
       (void)hipEventDestroy(e);
     }
   }
-  q->fov.release();
-  q->winMask.release();
   for (auto& v : q->hostDisp) {
     for (float* p : v) {
       if (p) {
@@ -663,17 +641,7 @@ void derp_seq_destroy(derp_seq* q) {
       (void)hipHostFree(p);
     }
   }
-  for (auto* vv : {&q->edgeColor, &q->edgeFg}) {
-    for (auto& v : *vv) {
-      for (auto& b : v) {
-        b.release();
-      }
-    }
-  }
-  for (auto& b : q->edgeRaw) {
-    b.release();
-  }
-  delete q;
+  delete q;  // every device buffer goes with it
 }
 
 int derp_seq_counts(const derp_seq* q, int* n_owned, int* n_halo) {
@@ -789,47 +757,36 @@ int derp_seq_selftest(derp_seq* q, int words) {
   RcclApi* api = rccl_api();
   HIPCHK(c, hipSetDevice(c->device));
   DevBuf a, b;
-  int rc = 0;
   const size_t bytes = (size_t)words * 4;
-  std::vector<uint32_t> h(words);
+  std::vector<uint32_t> h(words), got(words);
   const int next = (q->rank + 1) % q->world, prev = (q->rank + q->world - 1) % q->world;
   for (int i = 0; i < words; ++i) {
     h[i] = 0x9e3779b9u * (uint32_t)(i + 1) + (uint32_t)q->rank;
   }
-  if (a.ensure(bytes) || b.ensure(bytes)) {
-    rc = fail(c, "out of device memory");
-  } else if (hipMemcpyAsync(a.p, h.data(), bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-             hipMemsetAsync(b.p, 0, bytes, c->stream) != hipSuccess) {
-    rc = fail(c, "HIP error staging the self-test");
-  } else {
-    ncclResult_t r = api->GroupStart();
-    if (r == ncclSuccess) {
-      r = api->Send(a.p, bytes, ncclUint8, next, q->comm, c->stream);
-    }
-    if (r == ncclSuccess) {
-      r = api->Recv(b.p, bytes, ncclUint8, prev, q->comm, c->stream);
-    }
-    const ncclResult_t e = api->GroupEnd();
-    if (r == ncclSuccess) {
-      r = e;
-    }
-    std::vector<uint32_t> got(words);
-    if (r != ncclSuccess) {
-      rc = fail(c, "RCCL self-test: %s", api->GetErrorString(r));
-    } else if (hipStreamSynchronize(c->stream) != hipSuccess ||
-               hipMemcpy(got.data(), b.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = fail(c, "HIP error reading the self-test back: %s", hipGetErrorString(hipGetLastError()));
-    } else {
-      for (int i = 0; i < words && !rc; ++i) {
-        if (got[i] != 0x9e3779b9u * (uint32_t)(i + 1) + (uint32_t)prev) {
-          rc = fail(c, "RCCL self-test: word %d from rank %d is %08x", i, prev, got[i]);
-        }
-      }
+  TRY(upload_sync(c, a, h.data(), bytes));
+  ALLOC(c, b, bytes);
+  HIPCHK(c, hipMemsetAsync(b.p, 0, bytes, c->stream));
+  ncclResult_t r = api->GroupStart();
+  if (r == ncclSuccess) {
+    r = api->Send(a.p, bytes, ncclUint8, next, q->comm, c->stream);
+  }
+  if (r == ncclSuccess) {
+    r = api->Recv(b.p, bytes, ncclUint8, prev, q->comm, c->stream);
+  }
+  const ncclResult_t e = api->GroupEnd();  // always closed, also on the error path
+  if (r == ncclSuccess) {
+    r = e;
+  }
+  if (r != ncclSuccess) {
+    return fail(c, "RCCL self-test: %s", api->GetErrorString(r));
+  }
+  TRY(download_sync(c, got.data(), b.p, bytes));
+  for (int i = 0; i < words; ++i) {
+    if (got[i] != 0x9e3779b9u * (uint32_t)(i + 1) + (uint32_t)prev) {
+      return fail(c, "RCCL self-test: word %d from rank %d is %08x", i, prev, got[i]);
     }
   }
-  a.release();
-  b.release();
-  return rc;
+  return 0;
 }
 
 // ---- out-of-core helpers ------------------------------------------------------------------------
@@ -838,8 +795,8 @@ namespace {
 
 // BGR u16 host plane -> BGRX texels of `dst` plane s (what derp_upload_color does for the selected slot)
 int upload_color_plane(derp_ctx* c, DevBuf& dst, int s, const uint16_t* bgr, size_t n) {
-  TRY(upload_tmp(c, c->staging, bgr, n * 3));
-  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->staging.as<uint16_t>(),
+  TRY(upload_tmp(c, c->w.staging, bgr, n * 3));
+  hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->w.staging.as<uint16_t>(),
                      dst.as<ushort4>() + (size_t)s * n, n);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));  // the staging buffer is reused by the next plane
@@ -899,14 +856,14 @@ int stream_in_level(derp_seq* q, int k, int level, bool forCompute) {
   }
   const size_t n = npx(c, level);
   for (int s = 0; s < c->S; ++s) {
-    TRY(upload_color_plane(c, c->pyrColor[level], s, h->color + (size_t)s * n * 3, n));
+    TRY(upload_color_plane(c, c->frame().color[level], s, h->color + (size_t)s * n * 3, n));
   }
   if (h->fg) {
-    HIPCHK(c, hipMemcpy(c->pyrFg[level].p, h->fg, n * c->S, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->frame().fg[level].p, h->fg, n * c->S, hipMemcpyHostToDevice));
   }
   if (forCompute && h->bg) {
-    HIPCHK(c, hipMemcpy(c->pyrBg[level].p, h->bg, n * c->D * sizeof(float), hipMemcpyHostToDevice));
-    c->haveBg[level] = 1;
+    HIPCHK(c, hipMemcpy(c->frame().bg[level].p, h->bg, n * c->D * sizeof(float), hipMemcpyHostToDevice));
+    c->frame().haveBg[level] = 1;
   }
   return 0;
 }
@@ -927,23 +884,23 @@ int stream_compute_frame(derp_seq* q, int level, int k) {
     if (!q->hostHave[(size_t)k * c->numLevels + up]) {
       return fail(c, "Missing disparity of level %d needed to start level %d (frame %d)", up, level, q->owned[k]);
     }
-    HIPCHK(c, hipMemcpy(c->pyrDisp[up].p, q->hostDisp[k][up], npx(c, up) * c->D * sizeof(float), hipMemcpyHostToDevice));
-    c->haveDisp[up] = 1;
+    HIPCHK(c, hipMemcpy(c->frame().disp[up].p, q->hostDisp[k][up], npx(c, up) * c->D * sizeof(float), hipMemcpyHostToDevice));
+    c->frame().haveDisp[up] = 1;
     if (c->opt.use_foreground_masks) {  // the masked upsample reads the coarse mask too (DerpCLI.cpp:280-285)
       const derp_seq::HostIn* hu;
       TRY(host_inputs_of(q, k, up, &hu));
       if (hu->fg) {
-        HIPCHK(c, hipMemcpy(c->pyrFg[up].p, hu->fg, npx(c, up) * c->S, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->frame().fg[up].p, hu->fg, npx(c, up) * c->S, hipMemcpyHostToDevice));
       }
     }
   }
   TRY(process_level(c, level));
   const size_t bytes = npx(c, level) * c->D * sizeof(float);
   float* out = q->opt.do_temporal_filter ? q->hostRaw[k] : q->hostDisp[k][level];
-  HIPCHK(c, hipMemcpyAsync(out, c->pyrDisp[level].p, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(out, c->frame().disp[level].p, bytes, hipMemcpyDeviceToHost, c->stream));
   const int ei = edge_index(q, q->owned[k]);
   if (ei >= 0) {
-    HIPCHK(c, hipMemcpyAsync(q->edgeRaw[ei].p, c->pyrDisp[level].p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(q->edgeRaw[ei].p, c->frame().disp[level].p, bytes, hipMemcpyDeviceToDevice, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   tag.k = k;
@@ -977,14 +934,13 @@ int stream_filter_level(derp_seq* q, int level, int W, int H, int radius) {
             tag = derp_seq::SlotTag();
             TRY(stream_in_level(q, ku, level, false));
           }
-          HIPCHK(c, hipMemcpy(c->pyrDisp[level].p, q->hostRaw[ku], n * c->D * sizeof(float), hipMemcpyHostToDevice));
+          HIPCHK(c, hipMemcpy(c->frame().disp[level].p, q->hostRaw[ku], n * c->D * sizeof(float), hipMemcpyHostToDevice));
           tag.k = ku;
           tag.colorLevel = tag.rawLevel = level;
         }
-        SlotView v = slot_view(c, slot);
-        pc = (*v.color)[level].p;
-        pd = (*v.disp)[level].p;
-        pm = (*v.fg)[level].p;
+        pc = c->frames[slot].color[level].p;
+        pd = c->frames[slot].disp[level].p;
+        pm = c->frames[slot].fg[level].p;
       } else {
         void* p;
         size_t b;
@@ -1052,14 +1008,14 @@ int derp_seq_host_inputs(derp_seq* q, int frame, int level, const uint16_t* colo
   const size_t n = npx(c, level);
   TRY(select_frame(c, k));
   for (int s = 0; color_bgr && s < c->S; ++s) {
-    TRY(upload_color_plane(c, c->pyrColor[level], s, color_bgr + (size_t)s * n * 3, n));
+    TRY(upload_color_plane(c, c->frame().color[level], s, color_bgr + (size_t)s * n * 3, n));
   }
   if (fg_masks) {
-    HIPCHK(c, hipMemcpy(c->pyrFg[level].p, fg_masks, n * c->S, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->frame().fg[level].p, fg_masks, n * c->S, hipMemcpyHostToDevice));
   }
   if (background_disparity) {
-    HIPCHK(c, hipMemcpy(c->pyrBg[level].p, background_disparity, n * c->D * sizeof(float), hipMemcpyHostToDevice));
-    c->haveBg[level] = 1;
+    HIPCHK(c, hipMemcpy(c->frame().bg[level].p, background_disparity, n * c->D * sizeof(float), hipMemcpyHostToDevice));
+    c->frame().haveBg[level] = 1;
   }
   return 0;
 }
@@ -1080,11 +1036,10 @@ int derp_seq_upload_color_plane(derp_seq* q, int frame, int level, int s, const 
   HIPCHK(c, hipSetDevice(c->device));
   // on the copy stream, into the frame's own slot: the frame computing on the main stream is another one
   const size_t n = npx(c, level);
-  SlotView v = slot_view(c, k);
   ALLOC(c, c->copyStaging, n * 3 * sizeof(uint16_t));
   HIPCHK(c, hipMemcpyAsync(c->copyStaging.p, bgr, n * 3 * sizeof(uint16_t), hipMemcpyHostToDevice, c->copyStream));
   hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->copyStream, c->copyStaging.as<uint16_t>(),
-                     (*v.color)[level].as<ushort4>() + (size_t)s * n, n);
+                     c->frames[k].color[level].as<ushort4>() + (size_t)s * n, n);
   KCHECK(c);
   HIPCHK(c, hipStreamSynchronize(c->copyStream));  // the staging buffer and `bgr` are free again
   return 0;
@@ -1135,11 +1090,11 @@ int derp_seq_download_disparity(derp_seq* q, int frame, int level, int d, float*
   HIPCHK(c, hipSetDevice(c->device));
   TRY(select_frame(c, k));
   if (d < 0) {  // every destination's plane in one copy, [D][h*w]
-    if (!c->haveDisp[level]) {
+    if (!c->frame().haveDisp[level]) {
       return fail(c, "level %d has not been processed", level);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(disp, c->pyrDisp[level].p, n * c->D * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(disp, c->frame().disp[level].p, n * c->D * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   }
   return derp_download_disparity(c, level, d, disp);
@@ -1236,7 +1191,7 @@ int derp_seq_level_provided_frame(derp_seq* q, int level, int frame) {
   // by the first plane and survives from an earlier run of the level
   const uint64_t all = c->D >= 64 ? ~0ull : (1ull << c->D) - 1;
   const size_t slotLevel = (size_t)k * c->numLevels + level;
-  if (!c->haveDisp[level] || q->uploaded.size() <= slotLevel || (q->uploaded[slotLevel] & all) != all) {
+  if (!c->frame().haveDisp[level] || q->uploaded.size() <= slotLevel || (q->uploaded[slotLevel] & all) != all) {
     return fail(c, "frame %d has no complete level %d disparity (derp_seq_upload_disparity of every destination first)", frame, level);
   }
   q->uploaded[slotLevel] = 0;
@@ -1253,7 +1208,7 @@ int derp_seq_level_provided_frame(derp_seq* q, int level, int frame) {
   return 0;
 }
 
-// How many work lanes (derp_ctx::WorkLane) the frames of `level` run on: 0 = one after the other on the context's
+// How many work lanes (WorkLane) the frames of `level` run on: 0 = one after the other on the context's
 // own working set. Coarse levels only (DERP_SEQ_LANE_MAX_WIDTH, default 256 px), frames resident, every destination's
 // tables in one batch; DERP_SEQ_LANES (default 8) = 0 / 1 switches the lanes off.
 int seq_lane_count(derp_seq* q, int level) {
@@ -1524,8 +1479,7 @@ int derp_seq_level_filter(derp_seq* q, int level) {
   // "Transfer" (pipeline.py:397-408): every owned frame is filtered before any raw level is overwritten — and (the join
   // above) no send of the exchange still reads one
   for (int k = 0; k < (int)q->owned.size(); ++k) {
-    SlotView v = slot_view(c, k);
-    HIPCHK(c, hipMemcpyAsync((*v.disp)[level].p, q->filtered[k].p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice,
+    HIPCHK(c, hipMemcpyAsync(c->frames[k].disp[level].p, q->filtered[k].p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice,
                              c->stream));
     q->computedAt[k] = -1;  // the slot holds the filtered level now: no window may read it as a raw level
   }

@@ -584,6 +584,61 @@ def test_frame_slots_and_dev_pointers(built):
     g.close()
 
 
+def test_frame_slots_grow_shrink_and_new_geometry(built):
+    """The slot vector grows by moving the resident pyramids (same device pointers, same contents), shrinks by
+    dropping the last slots, and a new geometry starts again from one slot whose results equal a fresh context's."""
+    from facebook360_dep_amd import derp, synth
+
+    n, res, rig, sizes = _setup("tiny")
+    g = derp.Derp(rig["cameras"], partial_coverage=1)
+    g.set_pyramid(sizes, res, res)
+    g.set_frame_slots(2)
+    for t in range(2):
+        g.select_frame(t)
+        g.upload_frame(synth.make_frame(rig, sizes, frame=t, seed=360 + t, device="cpu"))
+        g.process_pyramid()
+    g.synchronize()
+
+    def pointers(slot):
+        g.select_frame(slot)
+        return [g.dev_color(level, 1)[0] for level in (0, 1)] + [g.dev_disparity(level, 1)[0] for level in (0, 1)]
+
+    def disparities(slot):
+        g.select_frame(slot)
+        return [g.download_disparity(0, d) for d in range(n)]
+
+    ptrs = [pointers(t) for t in range(2)]
+    disp = [disparities(t) for t in range(2)]
+    assert g.frame_slots() == (2, 1)  # slot 1 is the selected one while the vector grows
+    g.set_frame_slots(4)
+    assert g.frame_slots() == (4, 0)
+    for t in range(2):
+        assert pointers(t) == ptrs[t]
+        assert all(_bad(a, b) == 0 for a, b in zip(disparities(t), disp[t]))
+    every = sum((pointers(t) for t in range(4)), [])
+    assert len(set(every)) == len(every) == 16 and 0 not in every
+    g.set_frame_slots(1)
+    assert g.frame_slots() == (1, 0)
+    assert pointers(0) == ptrs[0]
+    assert all(_bad(a, b) == 0 for a, b in zip(disparities(0), disp[0]))
+    with pytest.raises(derp.DerpError):
+        g.select_frame(1)
+    # another geometry: the finest level dropped, full size = the new finest level
+    sizes2 = sizes[1:]
+    frame2 = synth.make_frame(rig, sizes2, frame=0, seed=360, device="cpu")
+    fresh = derp.Derp(rig["cameras"], partial_coverage=1)
+    for ctx in (g, fresh):
+        ctx.set_pyramid(sizes2, sizes2[0][0], sizes2[0][1])
+        assert ctx.frame_slots() == (1, 0)
+        ctx.upload_frame(frame2)
+        ctx.process_pyramid()
+        ctx.synchronize()
+    for d in range(n):
+        assert _bad(g.download_disparity(0, d), fresh.download_disparity(0, d)) == 0
+    fresh.close()
+    g.close()
+
+
 def _gloo_worker(rank, world, port, out_dir):
     import torch
     import torch.distributed as dist
