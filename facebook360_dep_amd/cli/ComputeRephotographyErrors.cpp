@@ -126,8 +126,8 @@ int main(int argc, char** argv) {
     aX.ensure(nc * 3 * sizeof(float));
     aY.ensure(nc * 3 * sizeof(float));
     aScore.ensure(nc * 3 * sizeof(float));
-    float *cubeRef = static_cast<float*>(aRef.p), *cubeRender = static_cast<float*>(aRender.p);
-    float *x = static_cast<float*>(aX.p), *y = static_cast<float*>(aY.p), *score = static_cast<float*>(aScore.p);
+    float *cubeRef = aRef.as<float>(), *cubeRender = aRender.as<float>();
+    float *x = aX.as<float>(), *y = aY.as<float>(), *score = aScore.as<float>();
     std::vector<uint8_t> mask(nc);
     IoBatch plots;  // the PNG plots are encoded and written behind the next camera's rendering
     for (size_t i = 0; i < rig.size(); ++i) {
@@ -185,9 +185,6 @@ int main(int argc, char** argv) {
       plots.add(pool, [plot, plotPath, pw, ph] { write_png(plotPath, plot->data(), pw, ph, 3, 8); });
     }
     plots.wait();
-    for (Arena* a : {&aRef, &aRender, &aX, &aY, &aScore}) {
-      a->release();
-    }
     const int nCams = !only.empty() ? (int)only.size() : (int)rig.size();
     (void)used;
     for (int c = 0; c < 3; ++c) {

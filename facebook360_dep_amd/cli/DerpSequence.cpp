@@ -243,14 +243,7 @@ int main(int argc, char** argv) {
   J.create_output_dirs({"disparity_time_filtered_levels"});
   derp_ctx* ctx = J.ctx;
 
-  derp_seq_options so;
-  derp_seq_options_default(&so);
-  so.time_radius = F.i("time_radius");
-  so.sigma = (float)F.d("sigma");
-  so.weight_b = (float)F.d("weight_b");
-  so.weight_g = (float)F.d("weight_g");
-  so.weight_r = (float)F.d("weight_r");
-  so.space_radius = F.i("space_radius");
+  derp_seq_options so = seq_options_from_flags(F);
   so.use_foreground_masks = F.b("do_temporal_masking");
   so.do_temporal_filter = F.b("do_temporal_filter");
   so.partition = partition;
@@ -366,7 +359,12 @@ int main(int argc, char** argv) {
     // Per frame, not a running prefix: on a rank whose first owned frame reaches into another rank's chunk (every rank
     // but the first of a block partition, every rank of a cyclic one) that frame cannot be filtered before the level's
     // exchange, and the interior frames behind it still leave early.
-    std::vector<char> filtered(nOwned, 0), saved(nOwned, 0);
+    FilterAhead ahead(nOwned);
+    auto every = [](int) { return true; };
+    // PNG only at the finest level: the pipeline forces PFM above it (pipeline.py:366-369)
+    auto save = [&](int j, bool fromScratch) {
+      writer.save_seq(seq, owned[j], level, zero_pad(owned[j]), dirs, level == J.levelEnd, fromScratch);
+    };
     for (int k = 0; k < nOwned; ++k) {
       store.wait(k, level);  // this frame's level is decoded (the pool is busy with later frames / finer levels)
       Timer t;
@@ -376,26 +374,7 @@ int main(int argc, char** argv) {
       // (only at the two finest levels: above them a level's files are a few MB, and waiting for the GPU once per
       // frame instead of once per level costs more than they do)
       if (so.do_temporal_filter && level <= J.levelEnd + 1) {
-        std::vector<int> ready;  // filtered in an earlier iteration: their kernels ran before this frame's compute
-        for (int j = 0; j < nOwned; ++j) {
-          if (filtered[j] && !saved[j]) {
-            ready.push_back(j);
-          }
-        }
-        for (int j = 0; j <= k; ++j) {  // a frame's window never reaches past frame j + radius: later ones cannot be ready
-          if (!filtered[j]) {
-            const int rc = derp_seq_level_filter_frame(seq, level, owned[j]);
-            if (rc == 2) {
-              continue;  // its window is not complete yet (a later frame, or a halo frame the exchange brings)
-            }
-            DERP_OK(ctx, rc);
-            filtered[j] = 1;
-          }
-        }
-        for (int j : ready) {
-          writer.save_seq(seq, owned[j], level, zero_pad(owned[j]), dirs, level == J.levelEnd, true);
-          saved[j] = 1;
-        }
+        ahead.step(seq, ctx, level, owned, k, every, save);
       }
     }
     {
@@ -421,12 +400,7 @@ int main(int argc, char** argv) {
       DERP_OK(ctx, derp_synchronize(ctx));
       tCompute += t.s();
     }
-    for (int k = 0; k < nOwned; ++k) {
-      if (!saved[k]) {
-        // PNG only at the finest level: the pipeline forces PFM above it (pipeline.py:366-369)
-        writer.save_seq(seq, owned[k], level, zero_pad(owned[k]), dirs, level == J.levelEnd);
-      }
-    }
+    ahead.finish(owned, false, every, save);  // the whole level is filtered by now: from the frames' own level
     LOG_INFO(fmt("-- level %d: %.3fs (waited for decode %.3fs, input hand-over %.3fs, result downloads incl. waiting for "
                  "the GPU %.3fs, waited for a free download plane %.3fs)", level, total.s() - lv0, store.waited - dec0,
                  tUpload - up0, writer.downloading - dl0, writer.waited - wr0));

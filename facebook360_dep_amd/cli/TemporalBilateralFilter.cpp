@@ -140,14 +140,7 @@ static bool run_on_sequence_engine(Flags& F, const std::vector<derp_camera_desc>
       return false;
     }
   }
-  derp_seq_options so;
-  derp_seq_options_default(&so);
-  so.time_radius = R;
-  so.sigma = (float)F.d("sigma");
-  so.weight_b = (float)F.d("weight_b");
-  so.weight_g = (float)F.d("weight_g");
-  so.weight_r = (float)F.d("weight_r");
-  so.space_radius = F.i("space_radius");
+  derp_seq_options so = seq_options_from_flags(F);
   so.use_foreground_masks = useFg;
   so.do_temporal_filter = 1;
   derp_seq* seq = nullptr;
@@ -160,48 +153,22 @@ static bool run_on_sequence_engine(Flags& F, const std::vector<derp_camera_desc>
     fs::create_directories(DerpJob::levelDir(outDir, level) / cam.id);
   }
   const std::vector<fs::path> dirs{outDir};
-  std::vector<char> filtered(nOwned, 0), saved(nOwned, 0);
-  double tFilter = 0;
-  auto wanted = [&](int j) { return owned[j] >= first && owned[j] <= last; };
+  FilterAhead ahead(nOwned);
+  auto wanted = [&](int j) { return owned[j] >= first && owned[j] <= last; };  // the others only fill windows
+  auto save = [&](int j, bool fromScratch) {
+    writer.save_seq(seq, owned[j], level, zero_pad(owned[j]), dirs, true, fromScratch);
+  };
   for (int k = 0; k < nOwned; ++k) {
     store.wait(k, level);
     store.hand_over(seq, k, level, true);
     DERP_OK(ctx, derp_seq_level_provided_frame(seq, level, owned[k]));
-    std::vector<int> ready;  // filtered in an earlier iteration: written while this frame's filter runs
-    for (int j = 0; j < nOwned; ++j) {
-      if (filtered[j] && !saved[j]) {
-        ready.push_back(j);
-      }
-    }
-    Timer t;
-    for (int j = 0; j <= k; ++j) {
-      if (wanted(j) && !filtered[j]) {
-        const int rc = derp_seq_level_filter_frame(seq, level, owned[j]);
-        if (rc == 2) {
-          continue;  // a frame of its window is still to come
-        }
-        DERP_OK(ctx, rc);
-        filtered[j] = 1;
-      }
-    }
-    tFilter += t.s();
-    for (int j : ready) {
-      writer.save_seq(seq, owned[j], level, zero_pad(owned[j]), dirs, true, true);
-      saved[j] = 1;
-    }
+    ahead.step(seq, ctx, level, owned, k, wanted, save);  // earlier frames are written while this step's filter runs
   }
-  for (int j = 0; j < nOwned; ++j) {
-    if (wanted(j)) {
-      CHECK_MSG(filtered[j], fmt("frame %06d could not be filtered", owned[j]));
-      if (!saved[j]) {
-        writer.save_seq(seq, owned[j], level, zero_pad(owned[j]), dirs, true, true);
-      }
-    }
-  }
+  ahead.finish(owned, true, wanted, save);  // no level-wide filter follows: everything leaves from the filter's scratch
   writer.finish();
   LOG_INFO(fmt("-- filter: %d frame(s) of level %d read once each (%d I/O threads): waited for decode %.3fs, filter calls %.3fs, "
                "downloads incl. waiting for the GPU %.3fs, waited for writes %.3fs", nOwned, level, (int)pool.workers.size(),
-               store.waited, tFilter, writer.downloading, writer.waited));
+               store.waited, ahead.filterSeconds, writer.downloading, writer.waited));
   LOG_INFO(fmt("-- TOTAL: %.3fs wall", total.s()));
   derp_seq_destroy(seq);
   derp_destroy(ctx);
@@ -262,6 +229,7 @@ int main(int argc, char** argv) {
   const int level = F.i("level");
   const bool useFg = F.b("use_foreground_masks");
   auto levelDir = [&](const std::string& base) { return fs::path(base) / ("level_" + std::to_string(level)); };
+  // (a substring match, not parse_output_formats' tokens: what this path has always accepted)
   const bool savePng = F.s("output_formats").find("png") != std::string::npos;
   const bool saveExr = F.s("output_formats").find("exr") != std::string::npos;
 
@@ -314,13 +282,7 @@ int main(int argc, char** argv) {
       const fs::path dir = fs::path(F.s("output_root")) / "disparity_time_filtered_levels" /
           ("level_" + std::to_string(level)) / rigDst[cam].id;
       fs::create_directories(dir);
-      write_pfm(dir / (zero_pad(cur) + ".pfm"), out.data(), w, h);
-      if (savePng) {
-        write_disparity_png(dir / (zero_pad(cur) + ".png"), out.data(), w, h);
-      }
-      if (saveExr) {
-        write_exr_f32(dir / (zero_pad(cur) + ".exr"), out.data(), w, h);
-      }
+      write_disparity_files(dir, zero_pad(cur), out.data(), w, h, savePng, saveExr);
     }
   }
   LOG_INFO(fmt("-- TOTAL: %.3fs wall", total.s()));

@@ -124,19 +124,23 @@ int main(int argc, char** argv) {
       LOG_INFO("Saving output images...");
       const fs::path dir = fs::path(F.s("output")) / rigDst[i].id;
       fs::create_directories(dir);
+      // this tool's own reading of --output_formats: a leading dot is accepted, PFM only when named (or nothing is),
+      // unknown formats are skipped with a warning for every image
+      bool pfm = false, png = false, exr = false;
       std::stringstream ss(exts);
       std::string ext;
       while (std::getline(ss, ext, ',')) {
         if (ext == "pfm" || ext == ".pfm") {
-          write_pfm(dir / (frame + ".pfm"), up.data(), wUp, hUp);
+          pfm = true;
         } else if (ext == "png" || ext == ".png") {
-          write_disparity_png(dir / (frame + ".png"), up.data(), wUp, hUp);
+          png = true;
         } else if (ext == "exr" || ext == ".exr") {
-          write_exr_f32(dir / (frame + ".exr"), up.data(), wUp, hUp);
+          exr = true;
         } else if (!ext.empty()) {
           LOG_WARNING("output format not supported by this build: " + ext);
         }
       }
+      write_disparity_files(dir, frame, up.data(), wUp, hUp, png, exr, pfm);
     }
   }
   derp_destroy(ctx);

@@ -1,7 +1,8 @@
-// Host-side plumbing shared by the DerpCLI / TemporalBilateralFilter / UpsampleDisparity
-// executables: gflags-style flag parsing, glog-style logging with FATAL = exit(1), a small JSON
-// reader for rig files, PNG (zlib) and PFM I/O, directory helpers. Plain C++17 + zlib; the
-// reference uses gflags, glog, folly, boost::filesystem and OpenCV imgcodecs for the same jobs.
+// Host-side plumbing shared by the executables (DerpCLI, DerpSequence, TemporalBilateralFilter, UpsampleDisparity,
+// LayerDisparities, GenerateForegroundMasks, ComputeRephotographyErrors, SimpleMeshRenderer): gflags-style flag
+// parsing, glog-style logging with FATAL = exit(1), a small JSON reader for rig files, PNG (zlib), PFM and OpenEXR
+// I/O, directory helpers, the I/O worker pool. Plain C++17 + zlib; the reference uses gflags, glog, folly,
+// boost::filesystem and OpenCV imgcodecs for the same jobs.
 // All computation goes through the C-ABI in include/derp_hip.h.
 #pragma once
 #include <sched.h>
@@ -447,7 +448,8 @@ struct JsonParser {
   }
 };
 
-inline std::string read_file(const std::string& path) {  // "" when the file cannot be read
+// a whole file, two policies: "" when it cannot be read (the caller reports it in its own words) ...
+inline std::string read_file_or_empty(const fs::path& path) {
   std::string out;
   if (FILE* f = fopen(path.c_str(), "rb")) {
     if (fseek(f, 0, SEEK_END) == 0) {
@@ -461,10 +463,18 @@ inline std::string read_file(const std::string& path) {  // "" when the file can
   }
   return out;
 }
+// ... or fatal right here
+inline std::string read_file_or_die(const fs::path& path) {
+  std::ifstream f(path, std::ios::binary);
+  CHECK_MSG(f.good(), "failed to load image: " + path.string());
+  std::stringstream ss;
+  ss << f.rdbuf();
+  return ss.str();
+}
 
 // Camera::loadRig (Camera.cpp:244-258) -> the C-ABI's camera descriptions
 inline std::vector<derp_camera_desc> load_rig(const std::string& path) {
-  const std::string text = read_file(path);
+  const std::string text = read_file_or_empty(path);
   CHECK_MSG(!text.empty(), "could not read JSON file: " + path);
   JsonParser jp(text);
   const Json root = jp.value();
@@ -625,10 +635,7 @@ inline std::vector<float> read_pfm(const fs::path& path, int& w, int& h) {
 
 // ---------------------------------------------------------------- raster input (image_codecs.h) + PNG output
 // cv::imread picks its decoder by the file's signature; so does codecs::decode (PNG, JPEG, TIFF, BMP, PNM)
-using Png = codecs::Raster;  // w, h, channels (file order R, G, B [, A]), bitdepth 8 / 16 (32 = float samples in f32), px
-inline uint32_t be32(const unsigned char* p) {
-  return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3];
-}
+using codecs::Raster;  // w, h, channels (file order R, G, B [, A]), bitdepth 8 / 16 (32 = float samples in f32), px
 inline std::string read_head(const fs::path& path, size_t n) {
   std::ifstream f(path, std::ios::binary);
   std::string head(n, '\0');
@@ -645,18 +652,18 @@ inline bool raster_size(const fs::path& path, int& w, int& h) {
   if (head.size() < 4096) {
     return false;
   }
-  const std::string all = read_file(path.string());
+  const std::string all = read_file_or_empty(path);
   return codecs::probe_size(reinterpret_cast<const unsigned char*>(all.data()), all.size(), w, h);
 }
-inline Png read_raster(const fs::path& path) {
-  const std::string data = read_file(path.string());
+inline Raster read_raster(const fs::path& path) {
+  const std::string data = read_file_or_empty(path);
   CHECK_MSG(!data.empty(), "failed to load image: " + path.string());
   try {
     return codecs::decode(reinterpret_cast<const unsigned char*>(data.data()), data.size());
   } catch (const codecs::Error& e) {
     LOG_FATAL("failed to load image: " + path.string() + " (" + e.what() + ")");
   }
-  return Png();
+  return Raster();
 }
 inline void write_png(const fs::path& path, const uint16_t* px, int w, int h, int channels, int bitdepth) {
   const int bpp = channels * bitdepth / 8;
@@ -711,7 +718,7 @@ inline unsigned float_to_uint_sat(float v, float scale, unsigned maxv) {
   const double r = nearbyint((double)v * (double)scale);
   return !(r > 0) ? 0u : r >= (double)maxv ? maxv : (unsigned)r;
 }
-inline void raster_to_bgr16(const Png& p, const fs::path& path, uint16_t* out) {
+inline void raster_to_bgr16(const Raster& p, const fs::path& path, uint16_t* out) {
   if (p.bitdepth == 32) {  // a float image (one channel): convertTo(CV_16U, 65535 / 1.0), COLOR_GRAY2BGR
     CHECK_MSG(p.channels == 1 && p.f32.size() == (size_t)p.w * p.h, "unsupported float image as colour: " + path.string());
     for (size_t i = 0; i < p.f32.size(); ++i) {
@@ -733,7 +740,7 @@ inline void raster_to_bgr16(const Png& p, const fs::path& path, uint16_t* out) {
   }
 }
 inline void load_color_bgr16_into(const fs::path& path, uint16_t* out, int expectW, int expectH) {
-  const std::string data = read_file(path.string());
+  const std::string data = read_file_or_empty(path);
   CHECK_MSG(!data.empty(), "failed to load image: " + path.string());
   const codecs::Bytes bytes{reinterpret_cast<const unsigned char*>(data.data()), data.size()};
   int w = 0, h = 0;
@@ -747,12 +754,12 @@ inline void load_color_bgr16_into(const fs::path& path, uint16_t* out, int expec
     CHECK_MSG(w == expectW && h == expectH, "image size mismatch: " + path.string());
     return;
   }
-  const Png p = read_raster(path);
+  const Raster p = read_raster(path);
   CHECK_MSG(p.w == expectW && p.h == expectH, "image size mismatch: " + path.string());
   raster_to_bgr16(p, path, out);
 }
 inline std::vector<uint16_t> load_color_bgr16(const fs::path& path, int& w, int& h) {
-  const Png p = read_raster(path);
+  const Raster p = read_raster(path);
   w = p.w;
   h = p.h;
   std::vector<uint16_t> out((size_t)w * h * 3);
@@ -763,7 +770,7 @@ inline std::vector<uint16_t> load_color_bgr16(const fs::path& path, int& w, int&
 // COLOR_BGR[A]2GRAY of the 0 / 1 values — whose fixed-point weights (B 0.114, G 0.587, R 0.299, rounded) give 1 exactly
 // when the GREEN channel passed the threshold (G alone rounds to 1, B + R together to 0)
 inline std::vector<uint8_t> load_mask(const fs::path& path, int& w, int& h) {
-  const Png p = read_raster(path);
+  const Raster p = read_raster(path);
   w = p.w;
   h = p.h;
   std::vector<uint8_t> out((size_t)w * h);
@@ -856,22 +863,12 @@ inline bool exr_header(const std::string& data, const fs::path& path, ExrInfo& i
   info.tableOffset = pos + 1;
   return true;
 }
-inline std::string read_file(const fs::path& path) {
-  std::ifstream f(path, std::ios::binary);
-  CHECK_MSG(f.good(), "failed to load image: " + path.string());
-  std::stringstream ss;
-  ss << f.rdbuf();
-  return ss.str();
-}
 inline bool exr_size(const fs::path& path, int& w, int& h) {
-  std::ifstream f(path, std::ios::binary);
-  std::string head(4096, '\0');
-  f.read(&head[0], (std::streamsize)head.size());
-  head.resize((size_t)f.gcount());
+  const std::string head = read_head(path, 4096);
   ExrInfo info;
   if (!exr_header(head, path, info, false)) {
     // a header longer than the first 4 KB (many attributes) is still a valid file: parse all of it before giving up
-    if (head.size() < 4096 || !exr_header(read_file(path), path, info, false)) {
+    if (head.size() < 4096 || !exr_header(read_file_or_die(path), path, info, false)) {
       return false;
     }
   }
@@ -880,7 +877,7 @@ inline bool exr_size(const fs::path& path, int& w, int& h) {
   return true;
 }
 inline std::vector<float> read_exr_f32(const fs::path& path, int& w, int& h) {
-  const std::string data = read_file(path);
+  const std::string data = read_file_or_die(path);
   ExrInfo info;
   exr_header(data, path, info, true);
   w = info.w;
@@ -932,7 +929,7 @@ inline std::vector<float> load_float(const fs::path& path, int& w, int& h) {
   if (path.extension() == ".exr") {
     return read_exr_f32(path, w, h);
   }
-  const Png p = read_raster(path);
+  const Raster p = read_raster(path);
   w = p.w;
   h = p.h;
   if (p.bitdepth == 32) {  // a float TIFF: convertTo(CV_32F) of CV_32F is a copy
@@ -966,7 +963,6 @@ inline void write_exr_f32(const fs::path& path, const float* m, int w, int h, in
   std::string hdr;
   auto put = [&](const void* p, size_t n) { hdr.append(static_cast<const char*>(p), n); };
   auto put_i32 = [&](int32_t v) { put(&v, 4); };
-  auto put_f32 = [&](float v) { put(&v, 4); };
   auto attr = [&](const char* name, const char* type, const std::string& value) {
     hdr.append(name).push_back('\0');
     hdr.append(type).push_back('\0');
@@ -1003,7 +999,6 @@ inline void write_exr_f32(const fs::path& path, const float* m, int w, int h, in
     attr("screenWindowWidth", "float", std::string(reinterpret_cast<const char*>(&one), 4));
   }
   hdr.push_back('\0');  // end of the header
-  (void)put_f32;
   const int kLines = 16;
   const int blocks = (h + kLines - 1) / kLines;
   std::vector<std::string> chunks(blocks);
@@ -1069,6 +1064,28 @@ inline void write_disparity_png(const fs::path& path, const float* m, int w, int
     px[i] = !(v == v) ? 0 : v <= 0 ? 0 : v >= 65535.f ? 65535 : (uint16_t)lrintf(v);
   }
   write_png(path, px.data(), w, h, 1, 16);
+}
+// saveResults (PyramidLevel.h:494-519): one disparity plane as <dir>/<frameName>.pfm, plus .png and .exr on request
+inline void write_disparity_files(const fs::path& dir, const std::string& frameName, const float* disp, int w, int h,
+                                  bool png, bool exr, bool pfm = true) {
+  if (pfm) {
+    write_pfm(dir / (frameName + ".pfm"), disp, w, h);
+  }
+  if (png) {
+    write_disparity_png(dir / (frameName + ".png"), disp, w, h);
+  }
+  if (exr) {
+    write_exr_f32(dir / (frameName + ".exr"), disp, w, h);
+  }
+}
+// --output_formats, comma separated: which of the optional formats are named (PyramidLevel.h:515-516)
+inline void parse_output_formats(const std::string& formats, bool& png, bool& exr) {
+  std::stringstream ss(formats);
+  std::string f;
+  while (std::getline(ss, f, ',')) {
+    png |= f == "png";
+    exr |= f == "exr";
+  }
 }
 
 // getPyramidLevelSizes (Derp.cpp:72-99): level_N -> size of the first image found under it
@@ -1263,6 +1280,11 @@ struct IoBatch {
   bool done() {
     std::lock_guard<std::mutex> lk(mu);
     return pending == 0;
+  }
+  // every job has run; their errors, if any, stay where they are (for a destructor: nothing is raised)
+  void drain() {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [this] { return pending == 0; });
   }
   // the first error any finished job left, raised on the calling thread without waiting for the rest
   void raise_if_failed() {

@@ -62,12 +62,7 @@ struct DerpJob {
   static fs::path levelDir(const fs::path& base, int level) { return base / ("level_" + std::to_string(level)); }
   size_t npx(int level) const { return (size_t)W[level] * H[level]; }
 
-  // verifyInputs + rig + pyramid geometry (DerpCLI.cpp:69-218); `device` overrides --device when >= 0
-  void setup(int device = -1) {
-    setup_host();
-    setup_device(device);
-  }
-  // everything that needs no GPU: flags, rig, level sizes, input verification — image decoding can start right
+  // verifyInputs + rig + pyramid geometry (DerpCLI.cpp:69-218), in two steps. Everything that needs no GPU: flags, rig, level sizes, input verification — image decoding can start right
   // after it, while setup_device pays for the HIP start-up and the table allocations
   void setup_host() {
     CHECK_MSG(F.s("input_root") != "", "input_root");
@@ -104,9 +99,8 @@ struct DerpJob {
       std::string f;
       while (std::getline(ss, f, ',')) {
         CHECK_MSG(f.empty() || f == "exr" || f == "png" || f == "pfm", "Invalid output format specified: " + f);
-        savePng |= f == "png";
-        saveExr |= f == "exr";  // PyramidLevel.h:515-516; pfm is always written, like the reference (:494)
       }
+      parse_output_formats(F.s("output_formats"), savePng, saveExr);  // pfm is always written, like the reference (PyramidLevel.h:494)
       if (F.s("output_formats").empty()) {
         LOG_WARNING("No explicit output formats specified. Forcing PFM...");
       }
@@ -172,6 +166,7 @@ struct DerpJob {
       H[l] = sizes[l].second;
     }
   }
+  // `device` overrides --device when >= 0
   void setup_device(int device = -1) {
     // ---- context
     if (derp_create(&ctx, device >= 0 ? device : F.i("device"), rigSrc.data(), S, rigDst.data(), D) != 0) {
@@ -214,17 +209,53 @@ struct DerpJob {
   }
 };
 
-// host memory the uploads / downloads go through: page-locked when the runtime grants it
+
+// derp_seq_options from the six filter flags TemporalBilateralFilter and DerpSequence share (TemporalBilateralFilter.cpp:51-59)
+inline derp_seq_options seq_options_from_flags(const Flags& F) {
+  derp_seq_options so;
+  derp_seq_options_default(&so);
+  so.time_radius = F.i("time_radius");
+  so.sigma = (float)F.d("sigma");
+  so.weight_b = (float)F.d("weight_b");
+  so.weight_g = (float)F.d("weight_g");
+  so.weight_r = (float)F.d("weight_r");
+  so.space_radius = F.i("space_radius");
+  return so;
+}
+
+// Host memory the uploads / downloads go through and its owner: move-only, freed when the owner dies. Page-locked
+// when asked for and the runtime grants it, plain heap memory otherwise.
 struct Arena {
   void* p = nullptr;
   bool pinned = false;
   size_t bytes = 0;
-  void ensure(size_t n) {
+  Arena() = default;
+  Arena(const Arena&) = delete;
+  Arena& operator=(const Arena&) = delete;
+  Arena(Arena&& o) noexcept : p(o.p), pinned(o.pinned), bytes(o.bytes) {
+    o.p = nullptr;
+    o.bytes = 0;
+  }
+  Arena& operator=(Arena&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      pinned = o.pinned;
+      bytes = o.bytes;
+      o.p = nullptr;
+      o.bytes = 0;
+    }
+    return *this;
+  }
+  ~Arena() { release(); }
+  // grow-only; the contents are lost on growth and never initialised (a value-initialising container would write 4 GB
+  // of zeros before the first decode). pin = false: no call into the HIP runtime, which may not exist yet
+  void ensure(size_t n, bool pin = true) {
     if (n <= bytes) {
       return;
     }
     release();
-    p = derp_host_alloc(n);
+    p = pin ? derp_host_alloc(n) : nullptr;
     pinned = p != nullptr;
     if (!p) {
       p = malloc(n);
@@ -243,7 +274,60 @@ struct Arena {
     p = nullptr;
     bytes = 0;
   }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+  bool empty() const { return bytes == 0; }
 };
+
+// The decode jobs of one (frame, level), queued on `B` (loadLevelImages, ImageUtil.h:79-94; DerpCLI.cpp:235-248,
+// 276-303): colour [S][n][3], mask [S][n], background disparity [D][n] and the level's disparity from --disparity /
+// disparity_levels [D][n]; a null destination is skipped. dispExt: the extension of that last input ("" = the first
+// extension of its directory, i.e. whatever cv::imread would be given: ImageUtil.h:48-56).
+inline void queue_decode_jobs(const DerpJob& J, IoPool& pool, IoBatch& B, const std::string& frameName, int level,
+                              uint16_t* color, uint8_t* mask, float* bg, float* disp, const std::string& dispExt) {
+  const Flags& F = J.F;
+  const int w = J.W[level], h = J.H[level];
+  const size_t n = J.npx(level);
+  for (int s = 0; s < J.S; ++s) {
+    if (color) {
+      uint16_t* dst = color + n * 3 * s;
+      const fs::path path = image_path(DerpJob::levelDir(F.s("color"), level), J.rigSrc[s].id, frameName);
+      B.add(pool, [=] { load_color_bgr16_into(path, dst, w, h); });
+    }
+    if (mask) {
+      uint8_t* dst = mask + n * s;
+      const fs::path path = image_path(DerpJob::levelDir(F.s("foreground_masks"), level), J.rigSrc[s].id, frameName);
+      B.add(pool, [=] {
+        int mw, mh;
+        const std::vector<uint8_t> m = load_mask(path, mw, mh);
+        CHECK_MSG(mw == w && mh == h, "mask size mismatch: " + path.string());
+        memcpy(dst, m.data(), m.size());
+      });
+    }
+  }
+  for (int d = 0; bg && d < J.D; ++d) {
+    float* dst = bg + n * d;
+    const fs::path path = image_path(DerpJob::levelDir(F.s("background_disp"), level), J.rigDst[d].id, F.s("background_frame"));
+    B.add(pool, [=] {
+      int bw, bh;
+      const std::vector<float> m = load_float(path, bw, bh);
+      CHECK_MSG(bw == w && bh == h, "background disparity size mismatch: " + path.string());
+      memcpy(dst, m.data(), m.size() * 4);
+    });
+  }
+  for (int d = 0; disp && d < J.D; ++d) {
+    float* dst = disp + n * d;
+    const fs::path path = image_path(DerpJob::levelDir(J.dispLevels, level), J.rigDst[d].id, frameName, dispExt);
+    B.add(pool, [=] {
+      int pw, ph;
+      const std::vector<float> m = load_float(path, pw, ph);
+      CHECK_MSG(pw == w && ph == h, "previous-level disparity size mismatch: " + path.string());
+      memcpy(dst, m.data(), m.size() * 4);
+    });
+  }
+}
 
 // One frame's inputs (loadLevelImages, ImageUtil.h:79-94; DerpCLI.cpp:235-248,276-303): decoded by the pool into
 // one of two staging arenas, then uploaded into the context's SELECTED frame slot.
@@ -279,66 +363,25 @@ struct FrameStager {
       inBytes += J.npx(J.levelStart + 1) * 4 * J.D;
     }
   }
-  ~FrameStager() {
+  ~FrameStager() {  // no worker may still be decoding into the arenas when the members go
     batch[0].wait();
     batch[1].wait();
-    arena[0].release();
-    arena[1].release();
   }
 
   void start_decode(int frameNumber, int parity) {
     const std::string frameName = zero_pad(frameNumber);
-    Arena& A = arena[parity];
-    A.ensure(inBytes);
-    char* base = static_cast<char*>(A.p);
+    arena[parity].ensure(inBytes);
+    char* base = arena[parity].as<char>();
     IoBatch& B = batch[parity];
-    const DerpJob* j = &J;
-    const Flags& F = J.F;
     for (int level = inTop; level >= J.levelEnd; --level) {
-      const int w = J.W[level], h = J.H[level];
-      for (int s = 0; s < J.S; ++s) {
-        if (level <= J.levelStart) {
-          uint16_t* dst = reinterpret_cast<uint16_t*>(base + offColor[level]) + J.npx(level) * 3 * s;
-          const fs::path path = image_path(DerpJob::levelDir(F.s("color"), level), J.rigSrc[s].id, frameName);
-          B.add(pool, [=] { load_color_bgr16_into(path, dst, w, h); });
-        }
-        if (J.useFg) {
-          uint8_t* dst = reinterpret_cast<uint8_t*>(base + offMask[level]) + J.npx(level) * s;
-          const fs::path path = image_path(DerpJob::levelDir(F.s("foreground_masks"), level), J.rigSrc[s].id, frameName);
-          B.add(pool, [=] {
-            int mw, mh;
-            const std::vector<uint8_t> m = load_mask(path, mw, mh);
-            CHECK_MSG(mw == w && mh == h, "mask size mismatch: " + path.string());
-            memcpy(dst, m.data(), m.size());
-          });
-        }
-      }
-      if (J.useFg && level <= J.levelStart) {
-        for (int d = 0; d < J.D; ++d) {
-          float* dst = reinterpret_cast<float*>(base + offBg[level]) + J.npx(level) * d;
-          const fs::path path = image_path(DerpJob::levelDir(F.s("background_disp"), level), J.rigDst[d].id,
-                                           F.s("background_frame"));
-          B.add(pool, [=] {
-            int bw, bh;
-            const std::vector<float> bg = load_float(path, bw, bh);
-            CHECK_MSG(bw == w && bh == h, "background disparity size mismatch: " + path.string());
-            memcpy(dst, bg.data(), bg.size() * 4);
-          });
-        }
-      }
+      const bool compute = level <= J.levelStart;
+      queue_decode_jobs(J, pool, B, frameName, level, compute ? reinterpret_cast<uint16_t*>(base + offColor[level]) : nullptr,
+                        J.useFg ? reinterpret_cast<uint8_t*>(base + offMask[level]) : nullptr,
+                        J.useFg && compute ? reinterpret_cast<float*>(base + offBg[level]) : nullptr, nullptr, "");
     }
     if (J.levelStart < J.numLevels - 1) {  // resume: previous level from disk (DerpCLI.cpp:287-288)
-      const int level = J.levelStart + 1, w = J.W[level], h = J.H[level];
-      for (int d = 0; d < J.D; ++d) {
-        float* dst = reinterpret_cast<float*>(base + offPrev) + J.npx(level) * d;
-        const fs::path path = image_path(DerpJob::levelDir(j->dispLevels, level), J.rigDst[d].id, frameName, ".pfm");
-        B.add(pool, [=] {
-          int pw, ph;
-          const std::vector<float> prev = load_float(path, pw, ph);
-          CHECK_MSG(pw == w && ph == h, "previous-level disparity size mismatch: " + path.string());
-          memcpy(dst, prev.data(), prev.size() * 4);
-        });
-      }
+      queue_decode_jobs(J, pool, B, frameName, J.levelStart + 1, nullptr, nullptr, nullptr,
+                        reinterpret_cast<float*>(base + offPrev), ".pfm");
     }
   }
 
@@ -352,7 +395,7 @@ struct FrameStager {
   void upload(int parity) {
     Timer t;
     derp_ctx* ctx = J.ctx;
-    const char* base = static_cast<const char*>(arena[parity].p);
+    const char* base = arena[parity].as<const char>();
     for (int level = inTop; level >= J.levelEnd; --level) {
       for (int s = 0; s < J.S; ++s) {
         if (level <= J.levelStart) {
@@ -390,35 +433,11 @@ struct FrameStore {
   IoPool& pool;
   std::vector<int> frames;
   int inTop;
-  // uninitialised host memory (a value-initialising container would write 4 GB of zeros before the first decode)
-  template <typename T>
-  struct Raw {
-    T* p = nullptr;
-    size_t n = 0;
-    Raw() = default;
-    Raw(const Raw&) = delete;
-    Raw& operator=(const Raw&) = delete;
-    Raw(Raw&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
-    ~Raw() { free(p); }
-    void resize(size_t count) {
-      free(p);
-      p = static_cast<T*>(malloc(count * sizeof(T)));
-      CHECK_MSG(p != nullptr || count == 0, "out of host memory");
-      n = count;
-    }
-    void release() {
-      free(p);
-      p = nullptr;
-      n = 0;
-    }
-    T* data() const { return p; }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-  };
+  // unpinned: decoding starts before the HIP runtime exists, and a long sequence must not pin the host's RAM
   struct Level {
-    Raw<uint16_t> color;  // [S][n][3]
-    Raw<uint8_t> mask;    // [S][n]
-    Raw<float> bg, prev;  // [D][n]
+    Arena color;     // u16 [S][n][3]
+    Arena mask;      // u8 [S][n]
+    Arena bg, prev;  // f32 [D][n]
     std::unique_ptr<IoBatch> batch;
   };
   std::vector<std::vector<Level>> data;  // [frame index][level]
@@ -456,105 +475,54 @@ struct FrameStore {
     return (compute ? n * 6 * J.S : 0) + (J.useFg ? n * J.S + (compute ? n * 4 * J.D : 0) : 0) + (compute ? 0 : n * 4 * J.D);
   }
   void schedule(int k, int level) { pending.emplace_back(k, level); }
+  void start_next() {
+    const auto kl = pending.front();
+    pending.pop_front();
+    inFlight += level_bytes(kl.second);
+    started[kl.first][kl.second] = 1;
+    start_decode(kl.first, kl.second);
+  }
   // start queued decodes while they fit the budget (one is always allowed: progress)
   void pump() {
-    while (!pending.empty()) {
-      const auto kl = pending.front();
-      const size_t b = level_bytes(kl.second);
-      if (throttle && inFlight > 0 && inFlight + b > budget) {
-        break;
-      }
-      pending.pop_front();
-      inFlight += b;
-      started[kl.first][kl.second] = 1;
-      start_decode(kl.first, kl.second);
+    while (!pending.empty() && !(throttle && inFlight > 0 && inFlight + level_bytes(pending.front().second) > budget)) {
+      start_next();
     }
   }
-  ~FrameStore() {
+  ~FrameStore() {  // no worker may still be decoding into `data` when the members go; never raises
     for (auto& f : data) {
       for (auto& l : f) {
-        std::unique_lock<std::mutex> lk(l.batch->mu);
-        l.batch->cv.wait(lk, [&] { return l.batch->pending == 0; });
+        l.batch->drain();
       }
-    }
-    for (auto& b : bounce) {
-      b.release();
     }
   }
 
   void start_decode(int k, int level) {
-    const std::string frameName = zero_pad(frames[k]);
     Level& L = data[k][level];
-    IoBatch& B = *L.batch;
-    const Flags& F = J.F;
-    const int w = J.W[level], h = J.H[level];
     const size_t n = J.npx(level);
     const bool compute = level <= J.levelStart;  // level inTop > levelStart only feeds the upsample
+    const bool disp = !compute || J.filterOnly;  // resume: previous level from disk (DerpCLI.cpp:287-288); or the level to filter
     if (compute) {
-      L.color.resize(n * 3 * J.S);
+      L.color.ensure(n * 3 * J.S * sizeof(uint16_t), false);
     }
     if (J.useFg) {
-      L.mask.resize(n * J.S);
+      L.mask.ensure(n * J.S, false);
       if (compute && !J.filterOnly) {
-        L.bg.resize(n * J.D);
+        L.bg.ensure(n * J.D * sizeof(float), false);
       }
     }
-    for (int s = 0; s < J.S; ++s) {
-      if (compute) {
-        uint16_t* dst = L.color.data() + n * 3 * s;
-        const fs::path path = image_path(DerpJob::levelDir(F.s("color"), level), J.rigSrc[s].id, frameName);
-        B.add(pool, [=] { load_color_bgr16_into(path, dst, w, h); });
-      }
-      if (J.useFg) {
-        uint8_t* dst = L.mask.data() + n * s;
-        const fs::path path = image_path(DerpJob::levelDir(F.s("foreground_masks"), level), J.rigSrc[s].id, frameName);
-        B.add(pool, [=] {
-          int mw, mh;
-          const std::vector<uint8_t> m = load_mask(path, mw, mh);
-          CHECK_MSG(mw == w && mh == h, "mask size mismatch: " + path.string());
-          memcpy(dst, m.data(), m.size());
-        });
-      }
+    if (disp) {
+      L.prev.ensure(n * J.D * sizeof(float), false);
     }
-    if (J.useFg && compute && !J.filterOnly) {
-      for (int d = 0; d < J.D; ++d) {
-        float* dst = L.bg.data() + n * d;
-        const fs::path path = image_path(DerpJob::levelDir(F.s("background_disp"), level), J.rigDst[d].id,
-                                         F.s("background_frame"));
-        B.add(pool, [=] {
-          int bw, bh;
-          const std::vector<float> bg = load_float(path, bw, bh);
-          CHECK_MSG(bw == w && bh == h, "background disparity size mismatch: " + path.string());
-          memcpy(dst, bg.data(), bg.size() * 4);
-        });
-      }
-    }
-    if (!compute || J.filterOnly) {  // resume: previous level from disk (DerpCLI.cpp:287-288); or the level to filter
-      L.prev.resize(n * J.D);
-      for (int d = 0; d < J.D; ++d) {
-        float* dst = L.prev.data() + n * d;
-        // (the filter's input may be whatever cv::imread reads, first extension of the directory: ImageUtil.h:48-56)
-        const fs::path path = J.filterOnly ? image_path(DerpJob::levelDir(J.dispLevels, level), J.rigDst[d].id, frameName)
-                                           : image_path(DerpJob::levelDir(J.dispLevels, level), J.rigDst[d].id, frameName, ".pfm");
-        B.add(pool, [=] {
-          int pw, ph;
-          const std::vector<float> prev = load_float(path, pw, ph);
-          CHECK_MSG(pw == w && ph == h, "previous-level disparity size mismatch: " + path.string());
-          memcpy(dst, prev.data(), prev.size() * 4);
-        });
-      }
-    }
+    // (the filter's input may be whatever cv::imread reads: the first extension of the directory)
+    queue_decode_jobs(J, pool, *L.batch, zero_pad(frames[k]), level, L.color.as<uint16_t>(), L.mask.as<uint8_t>(),
+                      L.bg.as<float>(), L.prev.as<float>(), J.filterOnly ? "" : ".pfm");
   }
 
   void wait(int k, int level) {
     Timer t;
     while (!started[k][level]) {  // not started for lack of budget: the consumer is here, so it goes now
       CHECK_MSG(!pending.empty(), "frame level was never scheduled for decoding");
-      const auto kl = pending.front();
-      pending.pop_front();
-      inFlight += level_bytes(kl.second);
-      started[kl.first][kl.second] = 1;
-      start_decode(kl.first, kl.second);
+      start_next();
     }
     data[k][level].batch->wait();
     waited += t.s();
@@ -567,7 +535,15 @@ struct FrameStore {
   // on the library's copy stream, i.e. behind the compute of the frame before.
   // Out of core the library streams from the (pageable) buffers itself, whenever the frame's level is needed.
   static constexpr int kBounce = 4;
+  // Every level but the thumbnails goes through the page-locked bounce planes and the copy stream (the other path
+  // copies on the COMPUTE stream and waits for it).
+  static constexpr size_t kRingMinPlaneBytes = 64u << 10;
+  // Planes under 4 MB are copied into the bounce plane right there: a free pool thread can be a whole PNG inflation
+  // away. (Handing the runtime the pageable buffer directly — one call for all planes — took 25 ms per frame at the
+  // 256-px level while the inflation had every CPU busy.)
+  static constexpr size_t kPoolCopyPlaneBytes = 4u << 20;
   Arena bounce[kBounce];
+  IoBatch bounceReady[kBounce];
   // page-lock the bounce planes at the finest level's size once (on whichever thread calls this), not level by level
   void reserve_bounce(int level) {
     const size_t bytes = J.npx(level) * 3 * sizeof(uint16_t);
@@ -575,72 +551,62 @@ struct FrameStore {
       b.ensure(bytes);
     }
   }
-  IoBatch bounceReady[kBounce];
+  // `count` planes of `bytes` each through the ring: src(i) is plane i in pageable memory, upload(i, p) moves it from
+  // the page-locked p. Pool workers copy plane i + 1.. while plane i moves at the PCIe rate.
+  template <class Src, class Upload>
+  void through_bounce(int count, size_t bytes, Src src, Upload upload) {
+    const bool inlineCopy = bytes < kPoolCopyPlaneBytes;
+    auto stage = [&](int i) {
+      Arena& A = bounce[i % kBounce];
+      A.ensure(bytes);
+      void* dst = A.p;
+      const void* from = src(i);
+      if (inlineCopy) {
+        memcpy(dst, from, bytes);
+      } else {
+        bounceReady[i % kBounce].add(pool, [=] { memcpy(dst, from, bytes); }, 0);
+      }
+    };
+    for (int i = 0; i < std::min(kBounce, count); ++i) {
+      stage(i);
+    }
+    for (int i = 0; i < count; ++i) {
+      bounceReady[i % kBounce].wait();
+      upload(i, bounce[i % kBounce].p);
+      if (i + kBounce < count) {
+        stage(i + kBounce);
+      }
+    }
+  }
   void hand_over(derp_seq* seq, int k, int level, bool resident) {
     derp_ctx* ctx = J.ctx;
     Level& L = data[k][level];
-    const size_t plane = J.npx(level) * 3;  // u16 elements of one camera's image
-    // Every level but the thumbnails goes through the page-locked bounce planes and the copy stream (the other path
-    // copies on the COMPUTE stream and waits for it). Planes under 4 MB are copied into the bounce plane right here: a
-    // free pool thread can be a whole PNG inflation away. (Handing the runtime the pageable buffer directly — one
-    // call for all planes — took 25 ms per frame at the 256-px level while the inflation had every CPU busy.)
-    const bool ring = resident && !L.color.empty() && plane * sizeof(uint16_t) >= (64u << 10);
+    const int frame = frames[k];
+    const size_t dn = J.npx(level), plane = dn * 3;  // f32 / u16 elements of one camera's image
+    const bool ring = resident && !L.color.empty() && plane * sizeof(uint16_t) >= kRingMinPlaneBytes;
     if (ring) {
-      const bool inlineCopy = plane * sizeof(uint16_t) < (4u << 20);
-      auto stage = [&](int s) {
-        Arena& A = bounce[s % kBounce];
-        A.ensure(plane * sizeof(uint16_t));
-        void* dst = A.p;
-        const uint16_t* src = L.color.data() + plane * s;
-        if (inlineCopy) {
-          memcpy(dst, src, plane * sizeof(uint16_t));
-        } else {
-          bounceReady[s % kBounce].add(pool, [=] { memcpy(dst, src, plane * sizeof(uint16_t)); }, 0);
-        }
-      };
-      for (int s = 0; s < std::min(kBounce, J.S); ++s) {
-        stage(s);
-      }
-      for (int s = 0; s < J.S; ++s) {
-        bounceReady[s % kBounce].wait();
-        DERP_OK(ctx, derp_seq_upload_color_plane(seq, frames[k], level, s, static_cast<const uint16_t*>(bounce[s % kBounce].p)));
-        if (s + kBounce < J.S) {
-          stage(s + kBounce);
-        }
-      }
+      through_bounce(J.S, plane * sizeof(uint16_t), [&](int s) { return L.color.as<uint16_t>() + plane * s; },
+                     [&](int s, const void* p) {
+                       DERP_OK(ctx, derp_seq_upload_color_plane(seq, frame, level, s, static_cast<const uint16_t*>(p)));
+                     });
     }
     if ((!ring && !L.color.empty()) || !L.mask.empty()) {
-      DERP_OK(ctx, derp_seq_host_inputs(seq, frames[k], level, ring || L.color.empty() ? nullptr : L.color.data(),
-                                        L.mask.empty() ? nullptr : L.mask.data(), L.bg.empty() ? nullptr : L.bg.data()));
+      DERP_OK(ctx, derp_seq_host_inputs(seq, frame, level, ring ? nullptr : L.color.as<uint16_t>(), L.mask.as<uint8_t>(),
+                                        L.bg.as<float>()));
     }
     if (!L.prev.empty()) {
-      const size_t dn = J.npx(level);
-      if (ring && J.filterOnly) {
-        // the level to filter is as large as the colour: through the same page-locked planes (a float plane fits a
-        // colour plane's 6 bytes per pixel), pool workers copying plane d + 1.. while plane d moves at the PCIe rate
-        const bool inlineCopy = dn * sizeof(float) < (4u << 20);
-        auto stage = [&](int d) {
-          void* dst = bounce[d % kBounce].p;
-          const float* src = L.prev.data() + dn * d;
-          if (inlineCopy) {
-            memcpy(dst, src, dn * sizeof(float));
-          } else {
-            bounceReady[d % kBounce].add(pool, [=] { memcpy(dst, src, dn * sizeof(float)); }, 0);
-          }
-        };
-        for (int d = 0; d < std::min(kBounce, J.D); ++d) {
-          stage(d);
-        }
-        for (int d = 0; d < J.D; ++d) {
-          bounceReady[d % kBounce].wait();
-          DERP_OK(ctx, derp_seq_upload_disparity(seq, frames[k], level, d, static_cast<const float*>(bounce[d % kBounce].p)));
-          if (d + kBounce < J.D) {
-            stage(d + kBounce);
-          }
-        }
+      // ring && filterOnly: the level to filter is as large as the colour: through the same page-locked planes (a
+      // float plane fits a colour plane's 6 bytes per pixel)
+      const bool viaRing = ring && J.filterOnly;
+      auto upload = [&](int d, const void* p) {
+        DERP_OK(ctx, derp_seq_upload_disparity(seq, frame, level, d, static_cast<const float*>(p)));
+      };
+      auto src = [&](int d) { return L.prev.as<float>() + dn * d; };
+      if (viaRing) {
+        through_bounce(J.D, dn * sizeof(float), src, upload);
       } else {
         for (int d = 0; d < J.D; ++d) {
-          DERP_OK(ctx, derp_seq_upload_disparity(seq, frames[k], level, d, L.prev.data() + dn * d));
+          upload(d, src(d));
         }
       }
     }
@@ -655,6 +621,60 @@ struct FrameStore {
   }
 };
 
+// Filter a frame as soon as its window is complete (derp_seq_level_filter_frame) and hand it to `save` one step
+// later: its kernels were queued before that step's other GPU work, so its download does not wait for them.
+// Per frame, not a running prefix: a frame whose window reaches a frame that is still to come — or a halo frame the
+// level's exchange brings — stays unfiltered while the frames behind it leave early.
+struct FilterAhead {
+  std::vector<char> filtered, saved;
+  double filterSeconds = 0;  // inside derp_seq_level_filter_frame
+  explicit FilterAhead(int n) : filtered(n, 0), saved(n, 0) {}
+  // frame owned[k]'s level is in place: filter what became possible among the wanted frames 0..k (a frame's window
+  // never reaches past frame j + radius: later ones cannot be ready), then save(j, true) what an earlier step filtered
+  template <class Wanted, class Save>
+  void step(derp_seq* seq, derp_ctx* ctx, int level, const std::vector<int>& owned, int k, Wanted wanted, Save save) {
+    std::vector<int> ready;
+    for (size_t j = 0; j < owned.size(); ++j) {
+      if (filtered[j] && !saved[j]) {
+        ready.push_back((int)j);
+      }
+    }
+    Timer t;
+    for (int j = 0; j <= k; ++j) {
+      if (wanted(j) && !filtered[j]) {
+        const int rc = derp_seq_level_filter_frame(seq, level, owned[j]);
+        if (rc == 2) {
+          continue;  // its window is not complete yet
+        }
+        DERP_OK(ctx, rc);
+        filtered[j] = 1;
+      }
+    }
+    filterSeconds += t.s();
+    for (int j : ready) {
+      save(j, true);
+      saved[j] = 1;
+    }
+  }
+  // the wanted frames no step saved. fromScratch: they come from the filter's scratch too, so each must have been
+  // filtered by a step; otherwise the whole level was filtered since and they come from the frames' own level
+  template <class Wanted, class Save>
+  void finish(const std::vector<int>& owned, bool fromScratch, Wanted wanted, Save save) {
+    for (size_t j = 0; j < owned.size(); ++j) {
+      if (!wanted((int)j)) {
+        continue;
+      }
+      if (fromScratch) {
+        CHECK_MSG(filtered[j], fmt("frame %06d could not be filtered", owned[j]));
+      }
+      if (!saved[j]) {
+        save((int)j, fromScratch);
+        saved[j] = 1;
+      }
+    }
+  }
+};
+
 // saveResults (PyramidLevel.h:487-529): the selected frame's level is downloaded into page-locked memory and
 // written by the pool (PFM always, PNG on request) into every directory of `dirs`.
 struct LevelWriter {
@@ -664,14 +684,7 @@ struct LevelWriter {
   IoBatch batch[2];
   double waited = 0, downloading = 0;
   LevelWriter(const DerpJob& job, IoPool& p) : J(job), pool(p) {}
-  ~LevelWriter() {
-    finish();
-    arena[0].release();
-    arena[1].release();
-    for (auto& r : ring) {
-      r.mem.release();
-    }
-  }
+  ~LevelWriter() { finish(); }  // no worker may still be writing from the arenas / the ring when the members go
   // make arena[parity] (>= bytes) available: the files written from it earlier are on disk
   void begin(int parity, size_t bytes) {
     Timer t;
@@ -679,32 +692,30 @@ struct LevelWriter {
     waited += t.s();
     arena[parity].ensure(bytes);
   }
+  // the pool job that writes camera d's plane `disp` of `level` into every directory of `dirs`
+  std::function<void()> plane_job(int level, int d, const float* disp, const std::string& frameName,
+                                  const std::vector<fs::path>& dirs, bool png, bool exr) const {
+    const int w = J.W[level], h = J.H[level];
+    std::vector<fs::path> bases;
+    for (const auto& dir : dirs) {
+      bases.push_back(DerpJob::levelDir(dir, level) / J.rigDst[d].id);
+    }
+    return [=] {
+      for (const auto& base : bases) {
+        write_disparity_files(base, frameName, disp, w, h, png, exr);
+      }
+    };
+  }
   void save(int parity, size_t offset, int level, const std::string& frameName, const std::vector<fs::path>& dirs) {
     derp_ctx* ctx = J.ctx;
-    const int w = J.W[level], h = J.H[level];
-    const bool png = J.savePng, exr = J.saveExr;
     for (int d = 0; d < J.D; ++d) {
-      float* disp = reinterpret_cast<float*>(static_cast<char*>(arena[parity].p) + offset) + J.npx(level) * d;
+      float* disp = reinterpret_cast<float*>(arena[parity].as<char>() + offset) + J.npx(level) * d;
       {
         Timer t;
         DERP_OK(ctx, derp_download_disparity(ctx, level, d, disp));
         downloading += t.s();
       }
-      std::vector<fs::path> bases;
-      for (const auto& dir : dirs) {
-        bases.push_back(DerpJob::levelDir(dir, level) / J.rigDst[d].id);
-      }
-      batch[parity].add(pool, [=] {
-        for (const auto& base : bases) {
-          write_pfm(base / (frameName + ".pfm"), disp, w, h);
-          if (png) {
-            write_disparity_png(base / (frameName + ".png"), disp, w, h);
-          }
-          if (exr) {
-            write_exr_f32(base / (frameName + ".exr"), disp, w, h);
-          }
-        }
-      }, 1);
+      batch[parity].add(pool, plane_job(level, d, disp, frameName, dirs, J.savePng, J.saveExr), 1);
     }
   }
   // DerpSequence: a frame's level leaves through one of a few per-frame buffers — ONE download for all D planes (a
@@ -741,18 +752,7 @@ struct LevelWriter {
     }
     ringBatch.raise_if_failed();  // a write job of an earlier frame failed: stop here, not after the whole level
     waited += t.s();
-    Arena& A = ring[got].mem;
-    if (A.bytes < bytes) {
-      if (pinRing) {
-        A.ensure(bytes);
-      } else {
-        A.release();
-        A.p = malloc(bytes);
-        CHECK_MSG(A.p != nullptr, "out of host memory");
-        A.pinned = false;
-        A.bytes = bytes;
-      }
-    }
+    ring[got].mem.ensure(bytes, pinRing);
     return got;
   }
   void ring_release(int i) {
@@ -771,11 +771,9 @@ struct LevelWriter {
   void save_seq(derp_seq* seq, int frame, int level, const std::string& frameName, const std::vector<fs::path>& dirs,
                 bool pngToo, bool fromScratch = false) {
     derp_ctx* ctx = J.ctx;
-    const int w = J.W[level], h = J.H[level];
-    const bool png = J.savePng && pngToo, exr = J.saveExr && pngToo;
     const size_t n = J.npx(level);
     const int slot = ring_acquire(n * sizeof(float) * J.D, J.D);
-    float* all = static_cast<float*>(ring[slot].mem.p);
+    float* all = ring[slot].mem.as<float>();
     {
       Timer t;
       if (fromScratch) {
@@ -786,12 +784,8 @@ struct LevelWriter {
       downloading += t.s();
     }
     for (int d = 0; d < J.D; ++d) {
-      const float* disp = all + n * d;
-      std::vector<fs::path> bases;
-      for (const auto& dir : dirs) {
-        bases.push_back(DerpJob::levelDir(dir, level) / J.rigDst[d].id);
-      }
-      ringBatch.add(pool, [=] {
+      const std::function<void()> write = plane_job(level, d, all + n * d, frameName, dirs, J.savePng && pngToo, J.saveExr && pngToo);
+      ringBatch.add(pool, [this, slot, write] {
         // the slot goes back on EVERY exit path: a write that fails (disk full, unwritable output) throws, the batch
         // keeps the message, and ring_acquire / finish() on the host thread turn it into the fatal exit — a slot
         // that stayed taken would park the host thread in ring_acquire for ever instead
@@ -800,15 +794,7 @@ struct LevelWriter {
           int slot;
           ~Release() { w->ring_release(slot); }
         } release{this, slot};
-        for (const auto& base : bases) {
-          write_pfm(base / (frameName + ".pfm"), disp, w, h);
-          if (png) {
-            write_disparity_png(base / (frameName + ".png"), disp, w, h);
-          }
-          if (exr) {
-            write_exr_f32(base / (frameName + ".exr"), disp, w, h);
-          }
-        }
+        write();
       }, 1);
     }
   }

@@ -347,6 +347,109 @@ def test_derp_sequence_cli_equals_the_three_binary_pipeline(dataset, tmp_path):
     assert not os.path.exists(os.path.join(out_h, "disparity_levels", "level_1", ids[0], "000000.png"))
 
 
+def _same_files(dir_a, dir_b, what):
+    """Every file under dir_a/<cam>/ exists under dir_b/<cam>/ with the same bytes, and the other way round."""
+    cams = sorted(os.listdir(dir_a))
+    assert cams == sorted(os.listdir(dir_b)) and cams, what
+    for cam in cams:
+        files = sorted(os.listdir(os.path.join(dir_a, cam)))
+        assert files == sorted(os.listdir(os.path.join(dir_b, cam))) and files, (what, cam)
+        for f in files:
+            assert open(os.path.join(dir_a, cam, f), "rb").read() == open(os.path.join(dir_b, cam, f), "rb").read(), \
+                (what, cam, f)
+
+
+def test_derp_sequence_bounce_ring_with_inline_copies_and_plane_reuse(built, tmp_path):
+    """The hand-over of a resident frame's colour goes through the ring of four page-locked bounce planes only from
+    64 KiB per plane, which no `tiny` level reaches (96 x 96 x 6 B = 55 KB). `small` is the smallest configuration that
+    does: 160 x 160 x 6 B = 153,600 B at level 0, copied inline (under 4 MiB), and 6 planes for 4 bounce planes, so two
+    planes are reused. DerpSequence must still write, byte for byte, what the three binaries + Transfer write (their
+    uploads do not use the ring), and the out-of-core hand-over (no ring) must equal the resident one."""
+    import shutil
+
+    from facebook360_dep_amd import synth
+
+    root = str(tmp_path / "in")
+    n, res, widths = synth.config("small")
+    rig = synth.make_rig(n, res)
+    sizes = synth.level_sizes(res, res, widths)
+    assert n > 4 and sizes[0][0] * sizes[0][1] * 6 >= 64 << 10
+    synth.write_dataset(root, rig, [0, 1, 2], sizes)
+    rigf = os.path.join(root, "rigs", "rig_calibrated.json")
+    n_levels = len(sizes)
+    common_flags = ["--input_root=" + root, "--first=000000", "--last=000002", "--partial_coverage", "--resolution=%d" % res]
+    out_a = str(tmp_path / "a")
+    for level in range(n_levels - 1, -1, -1):
+        run("DerpCLI", *common_flags, "--output_root=" + out_a, "--level_start=%d" % level, "--level_end=%d" % level)
+        run("TemporalBilateralFilter", "--input_root=" + root, "--output_root=" + out_a, "--rig=" + rigf,
+            "--first=000000", "--last=000002", "--level=%d" % level)
+        src = os.path.join(out_a, "disparity_time_filtered_levels", "level_%d" % level)
+        dst = os.path.join(out_a, "disparity_levels", "level_%d" % level)
+        shutil.rmtree(dst)
+        shutil.copytree(src, dst)
+    out_b = str(tmp_path / "b")
+    p = run("DerpSequence", *common_flags, "--output_root=" + out_b)
+    assert "3 frame(s) owned, 0 halo frame(s), 3 frame slot(s) in HBM" in p.stderr and "(out of core)" not in p.stderr
+    for kind in ("disparity_levels", "disparity_time_filtered_levels"):
+        for level in range(n_levels):
+            name = os.path.join(kind, "level_%d" % level)
+            _same_files(os.path.join(out_a, name), os.path.join(out_b, name), name)
+    out_e, out_f = str(tmp_path / "e"), str(tmp_path / "f")
+    p = run("DerpSequence", *common_flags, "--output_root=" + out_e, "--time_radius=0", "--resident_frames=1")
+    assert "1 frame slot(s) in HBM (out of core)" in p.stderr
+    run("DerpSequence", *common_flags, "--output_root=" + out_f, "--time_radius=0")
+    for kind in ("disparity_levels", "disparity_time_filtered_levels"):
+        for level in range(n_levels):
+            name = os.path.join(kind, "level_%d" % level)
+            _same_files(os.path.join(out_e, name), os.path.join(out_f, name), name)
+
+
+def test_temporal_cli_bounce_ring_with_pool_staged_copies(built, tmp_path):
+    """The bounce ring stages a plane on the worker pool from 4 MiB: 1024 x 1024 is the smallest square at which a
+    float plane reaches that (exactly 4 MiB; the inline copy is for planes UNDER it), and a colour plane is 6 MiB
+    there. Five cameras for four bounce planes, so one is reused, for the colour and for the disparities alike. Nothing
+    is estimated: TemporalBilateralFilter alone, on seeded random raw disparities, on the sequence engine (ring) and
+    frame by frame (no ring) — every output file byte for byte the same."""
+    import json
+
+    from facebook360_dep_amd import imageio as dio
+    from facebook360_dep_amd import synth
+
+    n, res = 5, 1024
+    assert res * res * 4 >= 4 << 20 and (res - 1) * (res - 1) * 4 < 4 << 20
+    root = str(tmp_path / "in")
+    rig = synth.make_rig(n, res)
+    os.makedirs(os.path.join(root, "rigs"))
+    rigf = os.path.join(root, "rigs", "rig_calibrated.json")
+    with open(rigf, "w") as f:
+        json.dump(rig, f)
+    ids = [c["id"] for c in rig["cameras"]]
+    rng = np.random.default_rng(1024)
+    raw = str(tmp_path / "raw" / "disparity_levels")
+    for cam in ids:
+        cdir = os.path.join(root, "video", "color_levels", "level_0", cam)
+        ddir = os.path.join(raw, "level_0", cam)
+        os.makedirs(cdir)
+        os.makedirs(ddir)
+        for f in range(3):
+            # blocky colour (16-px cells: edges for the guide, and a PNG that deflates quickly) + per-pixel noise bits
+            cells = rng.integers(0, 65536 - 256, (res // 16, res // 16, 3), dtype=np.int64)
+            colour = np.kron(cells, np.ones((16, 16, 1), dtype=np.int64)) + rng.integers(0, 256, (res, res, 3))
+            dio.write_png16(os.path.join(cdir, "%06d.png" % f), colour.astype(np.uint16))
+            disp = rng.random((res, res), dtype=np.float32)
+            dio.write_pfm(os.path.join(ddir, "%06d.pfm" % f), np.maximum(disp, np.float32(1e-6)))  # (0, 1)
+    outs = {}
+    for mode in ("engine", "legacy"):
+        out = str(tmp_path / mode)
+        env = dict(os.environ, DERP_TBF_LEGACY="1") if mode == "legacy" else None
+        p = run("TemporalBilateralFilter", "--input_root=" + root, "--output_root=" + out, "--rig=" + rigf,
+                "--disparity=" + raw, "--level=0", "--first=000000", "--last=000002", "--time_radius=1", env=env)
+        assert ("read once each" in p.stderr) == (mode == "engine"), p.stderr[-2000:]
+        outs[mode] = os.path.join(out, "disparity_time_filtered_levels", "level_0")
+    _same_files(outs["legacy"], outs["engine"], "level_0")
+    assert sorted(os.listdir(os.path.join(outs["engine"], ids[0]))) == ["000000.pfm", "000001.pfm", "000002.pfm"]
+
+
 def test_derp_sequence_cli_masks_subset_and_resume(dataset, tmp_path):
     """DerpSequence with foreground masks + temporal masking (pipeline.py:386), a --cameras subset, and a
     resume from level 1 on disk (--level_start): against the oracle schedule."""
