@@ -102,6 +102,7 @@ EXPORTS = [
     "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
     "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
     "derp_render_vertices",
+    "derp_export_points", "derp_points_begin", "derp_points_splat", "derp_points_download", "derp_project_equirect_mask",
     "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
     "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
     "derp_get_counters", "derp_reset_counters", "derp_profile_enable", "derp_profile_reset", "derp_profile_query", "derp_profile_memoised",
@@ -510,6 +511,52 @@ class Derp:
         """camera `cam`'s mesh vertices after canopyVS's stereo stage (ipd 0: none) -> f32 [h, w, 4]."""
         out = np.zeros((shape[0], shape[1], 4), dtype=np.float32)
         self._ck(lib().derp_render_vertices(self.h, cam, C.c_float(ipd), _p(out)))
+        return out
+
+    # ---- conversion tools (source/conversion): cameras = this context's destinations, rescaled to the image size
+    def export_points(self, cam, disparity, color_bgr, max_depth=float("inf"), clip=False, subsample=1, cap=None):
+        """getPoints of ExportPointCloud for one camera: disparity f32 [h, w] + colour float BGR [h, w, 3] in 0..1
+        -> f32 [count, 6] rows of x y z r g b in row-major pixel order. `cap` (points) defaults to every pixel."""
+        disparity = np.ascontiguousarray(disparity, dtype=np.float32)
+        color_bgr = np.ascontiguousarray(color_bgr, dtype=np.float32)
+        h, w = disparity.shape
+        assert color_bgr.shape == (h, w, 3)
+        cap = h * w if cap is None else cap
+        out = np.zeros((cap, 6), dtype=np.float32)
+        count = C.c_size_t()
+        rc = lib().derp_export_points(self.h, cam, _p(disparity), w, h, _p(color_bgr), C.c_double(max_depth), int(clip),
+                                      subsample, _p(out), C.c_size_t(cap), C.byref(count))
+        self.last_point_count = count.value
+        self._ck(rc)
+        return out[:count.value].copy()
+
+    def points_begin(self, sizes):
+        """One (w, h) per camera; the disparity images start at zero."""
+        assert len(sizes) == self.D
+        self._points_sizes = [tuple(s) for s in sizes]
+        w = (C.c_int * self.D)(*[s[0] for s in sizes])
+        h = (C.c_int * self.D)(*[s[1] for s in sizes])
+        self._ck(lib().derp_points_begin(self.h, w, h))
+
+    def points_splat(self, xyz, min_depth=0.0, max_depth=float("inf")):
+        """projectPointsToCameras of ImportPointCloud for one chunk of points f64 [n, 3]; chunks accumulate."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        self._ck(lib().derp_points_splat(self.h, _p(xyz), C.c_size_t(len(xyz)), C.c_double(min_depth),
+                                         C.c_double(max_depth)))
+
+    def points_download(self, cam):
+        sizes = getattr(self, "_points_sizes", [])
+        w, h = sizes[cam] if 0 <= cam < len(sizes) else (1, 1)  # (a bad index is the library's to refuse)
+        out = np.zeros((h, w), dtype=np.float32)
+        self._ck(lib().derp_points_download(self.h, cam, _p(out)))
+        return out
+
+    def project_equirect_mask(self, cam, eqr, w, h, depth=1000.0):
+        """ProjectEquirectsToCameras for one camera: equirect mask u8 [eh, ew] (non-zero = set) -> u8 {0,1} [h, w]."""
+        eqr = np.ascontiguousarray(eqr, dtype=np.uint8)
+        out = np.zeros((h, w), dtype=np.uint8)
+        self._ck(lib().derp_project_equirect_mask(self.h, cam, _p(eqr), eqr.shape[1], eqr.shape[0], w, h,
+                                                  C.c_double(depth), _p(out)))
         return out
 
     def fov_mask(self, d, w, h):

@@ -269,6 +269,30 @@ int derp_render_format_size(const char* format, int width, int height, int* out_
 int derp_render_format(derp_ctx* ctx, const char* format, const derp_render_params* p, const float* background,
                        const float* background_equirect, int eq_w, int eq_h, float* out_bgra);
 int derp_render_vertices(derp_ctx* ctx, int cam, float ipd, float* out_xyzw);
+/* ---- conversion tools at the depth stage's inputs and outputs (source/conversion) -------------------------------
+ * The cameras are the destinations of derp_create (a --cameras-filtered rig is passed as both src and dst); `cam`
+ * indexes them. Every call rescales the rig camera as the file holds it, Camera::rescale (Camera.cpp:217-223), to the
+ * image size it is given. No limit on the number of cameras beyond derp_create's.
+ * derp_export_points: getPoints (ExportPointCloud.cpp:67-137) for one camera. color_bgr = float [h][w][3] in 0..1,
+ *   already at the disparity's size. Pixels outside the image circle are dropped; depth > max_depth is dropped (clip)
+ *   or pulled back to max_depth; NaN / zero disparities are kept as IEEE arithmetic leaves them. Survivors come in
+ *   row-major pixel order, six floats each: x y z r g b. subsample > 1 keeps the pixels whose hash of (cam, pixel
+ *   index) is 0 modulo subsample: one in `subsample`, the same ones on every run (the reference's rand() from racing
+ *   threads is not reproducible). *count = the number of points; count > cap is an error that still reports it. */
+int derp_export_points(derp_ctx* ctx, int cam, const float* disparity, int w, int h, const float* color_bgr,
+                       double max_depth, int clip, int subsample, float* out_xyzrgb, size_t cap, size_t* count);
+/* projectPointsToCameras (ImportPointCloud.cpp:63-123): derp_points_begin sets one image size per camera and zeroes the
+ * images; derp_points_splat projects n points (rows of x y z) into every camera that sees them and keeps the largest
+ * 1 / |p| per pixel (|p| outside [min_depth, max_depth] counts as infinitely far), accumulating over any number of
+ * calls, in any chunking, to the same bits; it returns once the chunk is on the device, while its kernel runs.
+ * derp_points_download reads one camera's image [h][w] back. */
+int derp_points_begin(derp_ctx* ctx, const int* widths, const int* heights);
+int derp_points_splat(derp_ctx* ctx, const double* xyz, size_t n, double min_depth, double max_depth);
+int derp_points_download(derp_ctx* ctx, int cam, float* disparity);
+/* ProjectEquirectsToCameras.cpp:94-125 with image_util::worldToEquirect (ImageUtil.cpp:127-140): out [h][w] = the
+ * equirect mask (u8, non-zero = set) where the camera's pixel lands when projected at `depth` metres; {0,1}. */
+int derp_project_equirect_mask(derp_ctx* ctx, int cam, const uint8_t* eqr, int eqr_w, int eqr_h, int w, int h,
+                               double depth, uint8_t* out);
 /* generateFovMasks for one destination camera at an arbitrary size (DerpUtil.cpp:259-276) */
 int derp_fov_mask(derp_ctx* ctx, int dst, int w, int h, uint8_t* out);
 /* upsampleDisparities for one camera (UpsampleDisparityLib.cpp:98-182). fg_mask / fg_mask_up /
