@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -16,6 +17,7 @@
 
 #include "../../include/derp_hip.h"
 #include "derp_kernels.h"
+#include "derp_mesh.h"
 #include "derp_points.h"
 #include "derp_render.h"
 
@@ -150,6 +152,20 @@ struct SmrState {
   DevBuf zbuf, acc, big, nBig, cube, img, img2, tabs, back, equi, fetch, staging;
 };
 
+// derp_mesh_*: one camera's mesh (derp_mesh.h). The grid-sized buffers stay for the next camera; the compacted mesh
+// (V, F) and what the set-up gathers through (qmask, qoff, vorig) describe the mesh built last.
+struct MeshState {
+  DevBuf disparity, mask, tabs, vert, valid, qmask, used, blockFaces, blockVerts, offF, offV, totals, vmap, vorig, qoff, V, F;
+  DevBuf planes, costs, vq;
+  int W = 0, H = 0;
+  size_t nv = 0, nf = 0, nfUnmasked = 0;
+  bool built = false;
+  // derp_mesh_simplify's result (host): what the downloads return once it has run
+  bool simplified = false;
+  std::vector<double> sV;
+  std::vector<int32_t> sF;
+};
+
 }  // namespace
 
 struct derp_ctx {
@@ -159,6 +175,7 @@ struct derp_ctx {
   DevBuf copyStaging;                // their own staging buffer: they overlap the compute of the frame before
   DevBuf cnVert, cnRgba, cnZ, cnAcc, cnOut, cnBig, cnNBig;  // derp_canopy_cubemap's buffers, kept between calls
   std::unique_ptr<SmrState> smr;                            // derp_render_*'s scene (derp_render_upload)
+  std::unique_ptr<MeshState> mesh;                          // derp_mesh_*'s camera mesh (derp_mesh_build)
   std::string err;
   derp_options opt;
   int S = 0, D = 0;
@@ -2565,6 +2582,258 @@ int derp_project_equirect_mask(derp_ctx* c, int cam, const uint8_t* eqr, int eqr
                      m.as<uint8_t>());
   KCHECK(c);
   return download_sync(c, out, m.p, n);
+}
+
+// ---- ConvertToBinary's camera meshes (derp_mesh.h; the collapse loop is derp_simplify.cpp) ----
+namespace {
+// resizeNN's source index of every destination index (cv::resize INTER_NEAREST): min(floor(x * (1 / fx)), ssize - 1),
+// where fx is the scale the caller gave (cv::Size() + fx) or dsize / ssize (a given dsize)
+void nearest_table(int ssize, int dsize, double fx, int* out) {
+  const double ifx = 1. / fx;
+  for (int x = 0; x < dsize; ++x) {
+    out[x] = std::min((int)std::floor(x * ifx), ssize - 1);
+  }
+}
+int mesh_blocks(size_t n) {
+  return (int)((n + kMeshBlock - 1) / kMeshBlock);
+}
+int need_mesh(derp_ctx* c) {
+  if (!c) {
+    return 1;
+  }
+  if (!c->mesh || !c->mesh->built) {
+    return fail(c, "derp_mesh_build has not been called");
+  }
+  return 0;
+}
+// computeInitialQuadrics of the built mesh into m.planes / m.costs / m.vq
+int mesh_setup_dev(derp_ctx* c, int equi_error) {
+  MeshState& m = *c->mesh;
+  ALLOC(c, m.planes, std::max<size_t>(m.nf * 32, 8));
+  ALLOC(c, m.costs, std::max<size_t>(m.nf * 24, 8));
+  ALLOC(c, m.vq, std::max<size_t>(m.nv * derp_mesh::kQuadric * 8, 8));
+  if (m.nf == 0 || m.nv == 0) {
+    return 0;
+  }
+  hipLaunchKernelGGL(k_mesh_face_planes, dim3(mesh_blocks(m.nf)), dim3(kMeshBlock), 0, c->stream, m.V.as<double>(),
+                     m.F.as<int32_t>(), m.nf, m.planes.as<double>());
+  hipLaunchKernelGGL(k_mesh_vertex_quadrics, dim3(mesh_blocks(m.nv)), dim3(kMeshBlock), 0, c->stream, m.qmask.as<uint8_t>(),
+                     m.qoff.as<uint32_t>(), m.vorig.as<uint32_t>(), m.W, m.H, m.nv, m.planes.as<double>(), m.vq.as<double>());
+  hipLaunchKernelGGL(k_mesh_edge_costs, dim3(mesh_blocks(m.nf * 3)), dim3(kMeshBlock), 0, c->stream, m.V.as<double>(),
+                     m.F.as<int32_t>(), m.nf, m.vq.as<double>(), equi_error, m.costs.as<double>());
+  KCHECK(c);
+  return 0;
+}
+}  // namespace
+
+int derp_mesh_build(derp_ctx* c, int cam, const float* disparity, int w, int h, const double* resolution, double depth_scale,
+                    const uint8_t* mask, int mask_w, int mask_h, float tear_ratio) {
+  if (!c || !disparity || w <= 0 || h <= 0 || (size_t)w * h >= kMaxPixels || !(depth_scale > 0) ||
+      (mask && (mask_w <= 0 || mask_h <= 0 || (size_t)mask_w * mask_h >= kMaxPixels))) {
+    return fail(c, "bad arguments (null pointer, image size or depth scale)");
+  }
+  if (cam < 0 || cam >= c->D) {
+    return fail(c, "bad camera index %d (the context has %d)", cam, c->D);
+  }
+  // Camera::rescale(resolution) of the rig camera as the file holds it (resizeRig, ConvertToBinary.cpp:318-339), then
+  // getScalarFocal (Camera.cpp:185-188)
+  const derp_camera_desc& j = c->descDstH[cam];
+  double resx = j.resolution[0], resy = j.resolution[1], fx = j.focal[0], fy = j.focal[1];
+  if (resolution) {
+    fx *= resolution[0] / resx;
+    fy *= resolution[1] / resy;
+    resx = resolution[0];
+    resy = resolution[1];
+  }
+  if (fx != -fy) {
+    return fail(c, "Check failed: focal.x() == -focal.y() (%.17g vs. %.17g) pixels are not square", fx, -fy);
+  }
+  // cv::resize(depth, depth, cv::Size(), s, s, INTER_NEAREST) when s < 1: dsize = saturate_cast<int>(ssize * s)
+  const bool scaled = depth_scale < 1;
+  const int W = scaled ? (int)std::nearbyint(w * depth_scale) : w, H = scaled ? (int)std::nearbyint(h * depth_scale) : h;
+  if (W <= 0 || H <= 0) {
+    return fail(c, "depth scale %g leaves no pixels of a %d x %d map", depth_scale, w, h);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the mesh built before this one may still be read
+  if (!c->mesh) {
+    c->mesh.reset(new MeshState);
+  }
+  MeshState& m = *c->mesh;
+  m.built = m.simplified = false;
+  m.W = W;
+  m.H = H;
+  std::vector<int> tabs(2 * (size_t)W + 2 * (size_t)H);
+  int *xofs = tabs.data(), *yofs = xofs + W, *mxofs = yofs + H, *myofs = mxofs + W;
+  nearest_table(w, W, scaled ? depth_scale : 1.0, xofs);
+  nearest_table(h, H, scaled ? depth_scale : 1.0, yofs);
+  if (mask) {  // cv::resize(foregroundMask, foregroundMask, depth.size(), 0, 0, INTER_NEAREST)
+    nearest_table(mask_w, W, (double)W / mask_w, mxofs);
+    nearest_table(mask_h, H, (double)H / mask_h, myofs);
+  }
+  const size_t n = (size_t)W * H;
+  const int nb = mesh_blocks(n);
+  TRY(upload_sync(c, m.disparity, disparity, (size_t)w * h * 4));
+  TRY(upload_sync(c, m.tabs, tabs.data(), tabs.size() * 4));
+  if (mask) {
+    TRY(upload_sync(c, m.mask, mask, (size_t)mask_w * mask_h));
+  }
+  ALLOC(c, m.vert, n * 24);
+  ALLOC(c, m.valid, n);
+  ALLOC(c, m.qmask, n);
+  ALLOC(c, m.used, n);
+  ALLOC(c, m.blockFaces, (size_t)nb * 4);
+  ALLOC(c, m.blockVerts, (size_t)nb * 4);
+  ALLOC(c, m.offF, (size_t)nb * 8);
+  ALLOC(c, m.offV, (size_t)nb * 8);
+  ALLOC(c, m.totals, 24);
+  ALLOC(c, m.vmap, n * 4);
+  ALLOC(c, m.qoff, n * 4);
+  const int* dt = m.tabs.as<int>();
+  unsigned long long* totals = m.totals.as<unsigned long long>();  // kept faces, kept vertices, unmasked faces
+  HIPCHK(c, hipMemsetAsync(totals, 0, 24, c->stream));
+  hipLaunchKernelGGL(k_mesh_vertices, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.disparity.as<float>(), w, dt, dt + W, W, H,
+                     resx, resy, fx, mask ? m.mask.as<uint8_t>() : (const uint8_t*)nullptr, mask_w, dt + W + H,
+                     dt + 2 * W + H, m.vert.as<double>(), m.valid.as<uint8_t>());
+  hipLaunchKernelGGL(k_mesh_quads, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.vert.as<double>(), m.valid.as<uint8_t>(), W, H,
+                     tear_ratio, m.qmask.as<uint8_t>(), m.blockFaces.as<uint32_t>(), totals + 2);
+  hipLaunchKernelGGL(k_mesh_vertex_used, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.qmask.as<uint8_t>(), W, H,
+                     m.used.as<uint8_t>(), m.blockVerts.as<uint32_t>());
+  hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, m.blockFaces.as<uint32_t>(), nb,
+                     m.offF.as<unsigned long long>(), totals);
+  hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, m.blockVerts.as<uint32_t>(), nb,
+                     m.offV.as<unsigned long long>(), totals + 1);
+  KCHECK(c);
+  unsigned long long t[3] = {0, 0, 0};
+  TRY(download_sync(c, t, totals, 24));
+  m.nf = (size_t)t[0];
+  m.nv = (size_t)t[1];
+  m.nfUnmasked = (size_t)t[2];
+  if (m.nv > n || m.nf > 2 * n) {
+    return fail(c, "derp_mesh_build: inconsistent counts (%zu vertices, %zu faces for %zu pixels)", m.nv, m.nf, n);
+  }
+  ALLOC(c, m.vorig, std::max<size_t>(m.nv * 4, 8));
+  ALLOC(c, m.V, std::max<size_t>(m.nv * 24, 8));
+  ALLOC(c, m.F, std::max<size_t>(m.nf * 12, 8));
+  hipLaunchKernelGGL(k_mesh_vertex_scatter, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.vert.as<double>(), m.used.as<uint8_t>(),
+                     n, m.offV.as<unsigned long long>(), m.vmap.as<uint32_t>(), m.vorig.as<uint32_t>(), m.V.as<double>());
+  hipLaunchKernelGGL(k_mesh_face_scatter, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.qmask.as<uint8_t>(), W, H,
+                     m.offF.as<unsigned long long>(), m.vmap.as<uint32_t>(), m.qoff.as<uint32_t>(), m.F.as<int32_t>());
+  KCHECK(c);
+  m.built = true;
+  return 0;
+}
+
+int derp_mesh_counts(derp_ctx* c, size_t* vertices, size_t* faces, size_t* faces_unmasked) {
+  TRY(need_mesh(c));
+  const MeshState& m = *c->mesh;
+  if (vertices) {
+    *vertices = m.simplified ? m.sV.size() / 3 : m.nv;
+  }
+  if (faces) {
+    *faces = m.simplified ? m.sF.size() / 3 : m.nf;
+  }
+  if (faces_unmasked) {
+    *faces_unmasked = m.nfUnmasked;
+  }
+  return 0;
+}
+
+int derp_mesh_download_f64(derp_ctx* c, double* vertices, int32_t* faces) {
+  TRY(need_mesh(c));
+  const MeshState& m = *c->mesh;
+  if (m.simplified) {
+    if (vertices) {
+      memcpy(vertices, m.sV.data(), m.sV.size() * 8);
+    }
+    if (faces) {
+      memcpy(faces, m.sF.data(), m.sF.size() * 4);
+    }
+    return 0;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (vertices && m.nv) {
+    TRY(download_sync(c, vertices, m.V.p, m.nv * 24));
+  }
+  if (faces && m.nf) {
+    TRY(download_sync(c, faces, m.F.p, m.nf * 12));
+  }
+  return 0;
+}
+
+int derp_mesh_download(derp_ctx* c, int clamp_negative_z, float* vtx, uint32_t* idx) {
+  TRY(need_mesh(c));
+  size_t nv = 0, nf = 0;
+  TRY(derp_mesh_counts(c, &nv, &nf, nullptr));
+  std::vector<double> v(nv * 3);
+  std::vector<int32_t> f(nf * 3);
+  TRY(derp_mesh_download_f64(c, vtx ? v.data() : nullptr, idx ? f.data() : nullptr));
+  if (vtx) {
+    for (size_t i = 0; i < nv * 3; ++i) {
+      // "If depth is slightly negative ... we force this values to the minimum positive value" (:211-217), on the
+      // double, before writeDepth's cast<float>
+      vtx[i] = clamp_negative_z && i % 3 == 2 && v[i] < 0 ? FLT_MIN : (float)v[i];
+    }
+  }
+  if (idx) {
+    for (size_t i = 0; i < nf * 3; ++i) {
+      idx[i] = (uint32_t)f[i];
+    }
+  }
+  return 0;
+}
+
+int derp_mesh_setup(derp_ctx* c, int equi_error, double* face_planes, double* edge_costs, double* vertex_quadrics) {
+  TRY(need_mesh(c));
+  MeshState& m = *c->mesh;
+  if (m.simplified) {
+    return fail(c, "derp_mesh_setup: the mesh has been simplified (the set-up belongs to the mesh as built)");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  TRY(mesh_setup_dev(c, equi_error));
+  if (face_planes && m.nf) {
+    TRY(download_sync(c, face_planes, m.planes.p, m.nf * 32));
+  }
+  if (edge_costs && m.nf) {
+    TRY(download_sync(c, edge_costs, m.costs.p, m.nf * 24));
+  }
+  if (vertex_quadrics && m.nv) {
+    TRY(download_sync(c, vertex_quadrics, m.vq.p, m.nv * derp_mesh::kQuadric * 8));
+  }
+  return 0;
+}
+
+int derp_mesh_simplify(derp_ctx* c, int num_faces_out, float strictness, int remove_boundary_edges, int equi_error,
+                       int host_setup, int* stats) {
+  TRY(need_mesh(c));
+  MeshState& m = *c->mesh;
+  if (m.simplified) {
+    return fail(c, "derp_mesh_simplify: the mesh has been simplified already");
+  }
+  if (num_faces_out < 0) {
+    return fail(c, "derp_mesh_simplify: a negative face budget");
+  }
+  std::vector<double> V(m.nv * 3), planes, costs, vq;
+  std::vector<int32_t> F(m.nf * 3);
+  TRY(derp_mesh_download_f64(c, V.data(), F.data()));
+  if (!host_setup) {
+    planes.resize(m.nf * 4);
+    costs.resize(m.nf * 3);
+    vq.resize(m.nv * derp_mesh::kQuadric);
+    TRY(derp_mesh_setup(c, equi_error, planes.data(), costs.data(), vq.data()));
+  }
+  m.sV.resize(V.size());
+  m.sF.resize(F.size());
+  size_t nv = 0, nf = 0;
+  if (derp_mesh_simplify_host(V.data(), m.nv, F.data(), m.nf, host_setup ? nullptr : planes.data(),
+                              host_setup ? nullptr : costs.data(), host_setup ? nullptr : vq.data(), num_faces_out, strictness,
+                              remove_boundary_edges, equi_error, m.sV.data(), m.sF.data(), &nv, &nf, stats)) {
+    return fail(c, "derp_mesh_simplify_host refused the built mesh");
+  }
+  m.sV.resize(nv * 3);
+  m.sF.resize(nf * 3);
+  m.simplified = true;
+  return 0;
 }
 
 int derp_upsample_disparity(derp_ctx* c, int d, const float* disp, int w, int h, const float* bg_disp_up,

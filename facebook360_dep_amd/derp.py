@@ -103,6 +103,8 @@ EXPORTS = [
     "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
     "derp_render_vertices",
     "derp_export_points", "derp_points_begin", "derp_points_splat", "derp_points_download", "derp_project_equirect_mask",
+    "derp_mesh_build", "derp_mesh_counts", "derp_mesh_setup", "derp_mesh_simplify", "derp_mesh_download_f64", "derp_mesh_download",
+    "derp_mesh_setup_host", "derp_mesh_simplify_host",
     "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
     "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
     "derp_get_counters", "derp_reset_counters", "derp_profile_enable", "derp_profile_reset", "derp_profile_query", "derp_profile_memoised",
@@ -559,6 +561,52 @@ class Derp:
                                                   C.c_double(depth), _p(out)))
         return out
 
+    # ---- camera meshes (source/mesh_stream/ConvertToBinary.cpp:150-245): one mesh per context, the one built last
+    def mesh_build(self, cam, disparity, resolution=None, depth_scale=1.0, mask=None, tear_ratio=0.95):
+        """convertDepth up to applyMaskToVertexesAndFaces: disparity f32 [h, w], optional foreground mask u8 of any
+        size (non-zero = keep), `resolution` = what resizeRig hands Camera::rescale. -> (vertices, faces, faces
+        before the mask)."""
+        disparity = np.ascontiguousarray(disparity, dtype=np.float32)
+        h, w = disparity.shape
+        res = None if resolution is None else (C.c_double * 2)(float(resolution[0]), float(resolution[1]))
+        mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        mh, mw = (0, 0) if mask is None else mask.shape
+        self._ck(lib().derp_mesh_build(self.h, cam, _p(disparity), w, h, res, C.c_double(depth_scale), _p(mask), mw, mh,
+                                       C.c_float(tear_ratio)))
+        return self.mesh_counts()
+
+    def mesh_counts(self):
+        nv, nf, raw = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._ck(lib().derp_mesh_counts(self.h, C.byref(nv), C.byref(nf), C.byref(raw)))
+        return nv.value, nf.value, raw.value
+
+    def mesh_setup(self, equi_error=True):
+        """computeInitialQuadrics on the device -> (face planes f64 [nf, 4], edge costs [nf, 3], vertex quadrics [nv, 10])"""
+        nv, nf, _ = self.mesh_counts()
+        planes, costs, vq = np.zeros((nf, 4)), np.zeros((nf, 3)), np.zeros((nv, 10))
+        self._ck(lib().derp_mesh_setup(self.h, int(equi_error), _p(planes), _p(costs), _p(vq)))
+        return planes, costs, vq
+
+    def mesh_simplify(self, num_faces_out, strictness=0.2, remove_boundary_edges=False, equi_error=True, host_setup=False):
+        """MeshSimplifier::simplify of the built mesh -> (passes of the loop, DERP_MESH_EXIT_*)"""
+        stats = (C.c_int * 2)()
+        self._ck(lib().derp_mesh_simplify(self.h, num_faces_out, C.c_float(strictness), int(remove_boundary_edges),
+                                          int(equi_error), int(host_setup), stats))
+        return stats[0], stats[1]
+
+    def mesh_download_f64(self):
+        nv, nf, _ = self.mesh_counts()
+        v, f = np.zeros((nv, 3)), np.zeros((nf, 3), dtype=np.int32)
+        self._ck(lib().derp_mesh_download_f64(self.h, _p(v), _p(f)))
+        return v, f
+
+    def mesh_download(self, clamp_negative_z=False):
+        """the .vtx / .idx layouts: f32 [nv, 3], u32 [nf, 3]"""
+        nv, nf, _ = self.mesh_counts()
+        v, f = np.zeros((nv, 3), dtype=np.float32), np.zeros((nf, 3), dtype=np.uint32)
+        self._ck(lib().derp_mesh_download(self.h, int(clamp_negative_z), _p(v), _p(f)))
+        return v, f
+
     def fov_mask(self, d, w, h):
         out = np.zeros((h, w), dtype=np.uint8)
         self._ck(lib().derp_fov_mask(self.h, d, w, h, _p(out)))
@@ -681,6 +729,37 @@ class Derp:
         buf = C.create_string_buffer(256)
         self._ck(lib().derp_device_name(self.h, buf, 256))
         return buf.value.decode()
+
+
+MESH_EXIT_BUDGET, MESH_EXIT_INFINITE_THRESHOLD, MESH_EXIT_STUCK = 0, 1, 2
+
+
+def mesh_setup_host(vertices, faces, equi_error=True):
+    """computeInitialQuadrics on the host (no device) -> (face planes [nf, 4], edge costs [nf, 3], vertex quadrics [nv, 10])"""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    planes, costs, vq = np.zeros((len(f), 4)), np.zeros((len(f), 3)), np.zeros((len(v), 10))
+    if lib().derp_mesh_setup_host(_p(v), C.c_size_t(len(v)), _p(f), C.c_size_t(len(f)), int(equi_error), _p(planes),
+                                  _p(costs), _p(vq)):
+        raise DerpError("derp_mesh_setup_host: bad arguments")
+    return planes, costs, vq
+
+
+def mesh_simplify_host(vertices, faces, num_faces_out, strictness=0.2, remove_boundary_edges=False, equi_error=True,
+                       setup=None):
+    """MeshSimplifier::simplify on the host (no device); setup = (planes, costs, quadrics) or None: computed here.
+    -> (vertices f64 [nv', 3], faces i32 [nf', 3], (passes of the loop, MESH_EXIT_*))"""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    planes, costs, vq = (None, None, None) if setup is None else [np.ascontiguousarray(a, dtype=np.float64) for a in setup]
+    ov, of = np.zeros_like(v), np.zeros_like(f)
+    nv, nf = C.c_size_t(), C.c_size_t()
+    stats = (C.c_int * 2)()
+    if lib().derp_mesh_simplify_host(_p(v), C.c_size_t(len(v)), _p(f), C.c_size_t(len(f)), _p(planes), _p(costs), _p(vq),
+                                     num_faces_out, C.c_float(strictness), int(remove_boundary_edges), int(equi_error),
+                                     _p(ov), _p(of), C.byref(nv), C.byref(nf), stats):
+        raise DerpError("derp_mesh_simplify_host: bad arguments")
+    return ov[:nv.value].copy(), of[:nf.value].copy(), (stats[0], stats[1])
 
 
 def host_nth_element_pairs(pairs, nth):

@@ -293,6 +293,51 @@ int derp_points_download(derp_ctx* ctx, int cam, float* disparity);
  * equirect mask (u8, non-zero = set) where the camera's pixel lands when projected at `depth` metres; {0,1}. */
 int derp_project_equirect_mask(derp_ctx* ctx, int cam, const uint8_t* eqr, int eqr_w, int eqr_h, int w, int h,
                                double depth, uint8_t* out);
+/* ---- camera meshes (source/mesh_stream/ConvertToBinary.cpp:150-245) ----------------------------------------------
+ * derp_mesh_build: convertDepth up to applyMaskToVertexesAndFaces for camera `cam` of derp_create's destinations, on
+ *   the device: depth = 1.0f / disparity [h][w]; depth_scale < 1 resizes it with INTER_NEAREST (cv::resize with
+ *   cv::Size(), :166-169); mesh_util::getVertexesEquiError (MeshUtil.h:317-341); mesh_util::getFaces(wrap = false,
+ *   isRigCoordinates = false, tear_ratio) with getTriangleMask / addTriangle (:167-296); the vertex mask "depth is not
+ *   NaN", AND-ed with `mask` (u8 [mask_h][mask_w], non-zero = keep, INTER_NEAREST to the depth's size; NULL: none);
+ *   mesh_util::applyMaskToVertexesAndFaces (:345-405). `resolution` (double[2], NULL: as the rig file holds it) is
+ *   what resizeRig hands Camera::rescale (:318-339). Camera::getScalarFocal's focal.x == -focal.y is checked here.
+ *   The context holds one mesh: the one built last.
+ * derp_mesh_counts: vertices and faces of the mesh (after derp_mesh_simplify: of its result), and the faces getFaces
+ *   made before the mask removed any (the "Removed N of M faces" line, :191-198).
+ * derp_mesh_setup: MeshSimplifier::computeInitialQuadrics (MeshSimplifier.cpp:182-239) of the built mesh on the
+ *   device: face_planes [faces][4] (Face::normal and -normal.p0), edge_costs [faces][3] (Face::cost), vertex_quadrics
+ *   [vertices][10] (Vertex::q, the distinct entries q00 q01 q02 q03 q11 q12 q13 q22 q23 q33). NULL outputs are skipped.
+ * derp_mesh_simplify: MeshSimplifier(vertexes, faces, equi_error, threads = 1).simplify(num_faces_out, strictness,
+ *   remove_boundary_edges) (:456-562) of the built mesh: the set-up on the device (host_setup = 0) or on the host, the
+ *   collapse loop on the host (derp_mesh_simplify_host). stats (int[2], may be NULL): passes of the loop, and how it
+ *   ended (DERP_MESH_EXIT_*).
+ * derp_mesh_download_f64 / derp_mesh_download: MeshSimplifier::getVertexes / getFaces, or the built mesh when it was
+ *   not simplified; the second as mesh_util::writeDepth lays the files out (MeshUtil.h:72-89): float32 x y z rows and
+ *   uint32 index triples, with z < 0 raised to FLT_MIN first when clamp_negative_z (ConvertToBinary.cpp:211-217). */
+enum { DERP_MESH_EXIT_BUDGET = 0, DERP_MESH_EXIT_INFINITE_THRESHOLD = 1, DERP_MESH_EXIT_STUCK = 2 };
+int derp_mesh_build(derp_ctx* ctx, int cam, const float* disparity, int w, int h, const double* resolution,
+                    double depth_scale, const uint8_t* mask, int mask_w, int mask_h, float tear_ratio);
+int derp_mesh_counts(derp_ctx* ctx, size_t* vertices, size_t* faces, size_t* faces_unmasked);
+int derp_mesh_setup(derp_ctx* ctx, int equi_error, double* face_planes, double* edge_costs, double* vertex_quadrics);
+int derp_mesh_simplify(derp_ctx* ctx, int num_faces_out, float strictness, int remove_boundary_edges, int equi_error,
+                       int host_setup, int* stats);
+int derp_mesh_download_f64(derp_ctx* ctx, double* vertices, int32_t* faces);
+int derp_mesh_download(derp_ctx* ctx, int clamp_negative_z, float* vtx, uint32_t* idx);
+/* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
+ * range, a negative budget, more than 2^31 - 1 vertices or faces).
+ * derp_mesh_setup_host: computeInitialQuadrics over plain arrays: vertices f64 [nv][3], faces i32 [nf][3] -> the three
+ *   arrays of derp_mesh_setup.
+ * derp_mesh_simplify_host: MeshSimplifier::simplify + createFinalMesh (removeDeletedFaces, assignFaceVertexes,
+ *   identifyBoundaries, getThreshold, haveNormalsFlipped, commonFaces, updateCosts). The set-up arrays come from
+ *   derp_mesh_setup / derp_mesh_setup_host, or all three NULL: computed here. out_vertices / out_faces have room for
+ *   the input's counts. One departure: a pass that deleted nothing under a zero or NaN threshold repeats for ever in
+ *   the reference; here the loop ends (DERP_MESH_EXIT_STUCK). */
+int derp_mesh_setup_host(const double* vertices, size_t nv, const int32_t* faces, size_t nf, int equi_error,
+                         double* face_planes, double* edge_costs, double* vertex_quadrics);
+int derp_mesh_simplify_host(const double* vertices, size_t nv, const int32_t* faces, size_t nf, const double* face_planes,
+                            const double* edge_costs, const double* vertex_quadrics, int num_faces_out, float strictness,
+                            int remove_boundary_edges, int equi_error, double* out_vertices, int32_t* out_faces,
+                            size_t* out_nv, size_t* out_nf, int* stats);
 /* generateFovMasks for one destination camera at an arbitrary size (DerpUtil.cpp:259-276) */
 int derp_fov_mask(derp_ctx* ctx, int dst, int w, int h, uint8_t* out);
 /* upsampleDisparities for one camera (UpsampleDisparityLib.cpp:98-182). fg_mask / fg_mask_up /
