@@ -4,7 +4,8 @@
 // optionally .obj); then everything striped into fused_<i>.bin with a catalog (BinaryFusionUtil.h, StripedFile.h).
 // Compute = derp_mesh_build + derp_mesh_setup on the GPU per camera; the sequential collapse loop
 // (derp_mesh_simplify_host) runs on the I/O pool while the GPU builds the next camera's mesh. Fusion needs no device
-// and opens none. Not built: --output_formats bc7 (the ISPC codec) and pfm (writePfm's Eigen QR); both are refused
+// and opens none. --simplifier=parallel [extension] keeps a camera's mesh on the GPU instead: derp_mesh_simplify_parallel,
+// a pass-parallel collapse on the device, and the pool only writes the files. Not built: --output_formats bc7 (the ISPC codec) and pfm (writePfm's Eigen QR); both are refused
 // by name before anything is opened.
 #include <cfloat>
 #include <set>
@@ -336,8 +337,9 @@ static void fuse(const Flags& F, const std::vector<derp_camera_desc>& rig, const
 // ---------------------------------------------------------------- conversion
 struct Timings {
   std::mutex mu;
-  double build = 0, setup = 0, collapse = 0, write = 0, color = 0;
+  double build = 0, setup = 0, collapse = 0, write = 0, color = 0, parallel = 0;
   int meshes = 0;
+  long long parallelPasses = 0;
   void add(double& slot, double s) {
     std::lock_guard<std::mutex> lk(mu);
     slot += s;
@@ -406,6 +408,8 @@ int main(int argc, char** argv) {
   F.i32("threads", -1, "number of threads (-1 = max allowed, 0 = no threading)");
   F.i32("triangles", 150000, "number of triangles per camera mesh (<= 0: no simplification)");
   F.i32("device", 0, "HIP device index [extension]");
+  F.str("simplifier", "sequential", "[extension] mesh simplifier: sequential (the reference's collapse loop, on the host) or "
+                                    "parallel (pass-parallel collapses on the device)");
   F.parse(argc, argv);
 
   CHECK_MSG(F.d("color_scale") <= 1., "color_scale <= 1");
@@ -414,6 +418,12 @@ int main(int argc, char** argv) {
   CHECK_MSG(F.s("rig") != "", "rig");
   CHECK_MSG(F.s("first") != "", "first");
   CHECK_MSG(F.s("last") != "", "last");
+
+  const std::string simplifier = F.s("simplifier");
+  if (simplifier != "sequential" && simplifier != "parallel") {
+    LOG_FATAL("Invalid --simplifier=" + simplifier + " (sequential or parallel)");
+  }
+  const bool parallel = simplifier == "parallel";
 
   // verifyInputs' format check (:93-97), and the two formats this build does not have: before any file or device
   std::vector<std::string> formats;
@@ -549,12 +559,50 @@ int main(int argc, char** argv) {
                                      mask.empty() ? nullptr : mask.data(), mw, mh, (float)F.d("tear_ratio")));
         size_t nv = 0, nf = 0, nfAll = 0;
         DERP_OK(ctx, derp_mesh_counts(ctx, &nv, &nf, &nfAll));
-        auto V = std::make_shared<std::vector<double>>(nv * 3);
-        auto Fc = std::make_shared<std::vector<int32_t>>(nf * 3);
-        DERP_OK(ctx, derp_mesh_download_f64(ctx, V->data(), Fc->data()));
+        const bool onDevice = parallel && triangles > 0;  // the mesh leaves the device simplified
+        auto V = std::make_shared<std::vector<double>>(onDevice ? 0 : nv * 3);
+        auto Fc = std::make_shared<std::vector<int32_t>>(onDevice ? 0 : nf * 3);
+        if (!onDevice) {
+          DERP_OK(ctx, derp_mesh_download_f64(ctx, V->data(), Fc->data()));
+        }
         T.add(T.build, tb.s());
         LOG_INFO(fmt("Removed %zu of %zu faces (%.2f%%) corresponding to invalid depths and masked vertexes", nfAll - nf,
                      nfAll, 100.f * (nfAll - nf) / (float)nfAll));
+        if (onDevice) {
+          LOG_INFO(fmt("Target number of faces: %d", triangles));
+          Timer tp;
+          int stats[2] = {0, 0};
+          // the rules of MeshSimplifier(vertexes, faces, kIsEquierror, 1).simplify(triangles, 0.2, false)
+          DERP_OK(ctx, derp_mesh_simplify_parallel(ctx, triangles, 0.2f, 0, 1, stats));
+          size_t onv = 0, onf = 0;
+          DERP_OK(ctx, derp_mesh_counts(ctx, &onv, &onf, nullptr));
+          V->resize(onv * 3);
+          Fc->resize(onf * 3);
+          DERP_OK(ctx, derp_mesh_download_f64(ctx, V->data(), Fc->data()));
+          const double seconds = tp.s();
+          T.add(T.parallel, seconds);
+          T.parallelPasses += stats[0];
+          for (int pass = 0; pass < stats[0]; ++pass) {
+            derp_mesh_pass info;
+            DERP_OK(ctx, derp_mesh_parallel_pass(ctx, pass, &info));
+            LOG_INFO(fmt("Iter: %d, faces: %lld, threshold: %g", pass, info.faces, info.threshold));
+          }
+          static const char* kExit[] = {"the budget", "an infinite threshold", "a stuck threshold", "no candidate"};
+          LOG_INFO(fmt("Simplified frame %s, camera %s: %zu faces after %d passes in %.3f s on the device (ended by %s)",
+                       frameName.c_str(), camId.c_str(), onf, stats[0], seconds, kExit[stats[1] & 3]));
+          while (inFlight.size() >= maxInFlight) {
+            inFlight.front()->wait();
+            inFlight.pop_front();
+          }
+          inFlight.emplace_back(new IoBatch);
+          inFlight.back()->add(pool, [&F, &T, camId, frameName, V, Fc, saveMesh, saveObj] {
+            Timer tw;
+            write_mesh(F, camId, frameName, *V, *Fc, true, saveMesh, saveObj);
+            T.add(T.write, tw.s());
+          }, 1);
+          ++T.meshes;
+          continue;
+        }
         auto planes = std::make_shared<std::vector<double>>(), costs = std::make_shared<std::vector<double>>(),
              vq = std::make_shared<std::vector<double>>();
         if (triangles > 0) {
@@ -610,8 +658,9 @@ int main(int argc, char** argv) {
     if (T.meshes > 0) {
       const double n = T.meshes;
       LOG_INFO(fmt("Timing: %d camera meshes in %.3f s wall; per mesh: device build %.4f s, device set-up %.4f s, host "
-                   "collapse %.4f s, file writes %.4f s",
-                   T.meshes, wall.s(), T.build / n, T.setup / n, T.collapse / n, T.write / n));
+                   "collapse %.4f s, file writes %.4f s, device simplifier %.4f s in %.1f passes",
+                   T.meshes, wall.s(), T.build / n, T.setup / n, T.collapse / n, T.write / n, T.parallel / n,
+                   T.parallelPasses / n));
     }
     fs::create_directories(F.s("bin"));
     save_rig(fs::path(F.s("bin")) / (fs::path(F.s("rig")).stem().string() + "_fused.json"), rig,

@@ -15,6 +15,8 @@
 #include <string>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "../../include/derp_hip.h"
 #include "derp_kernels.h"
 #include "derp_mesh.h"
@@ -160,10 +162,14 @@ struct MeshState {
   int W = 0, H = 0;
   size_t nv = 0, nf = 0, nfUnmasked = 0;
   bool built = false;
-  // derp_mesh_simplify's result (host): what the downloads return once it has run
+  // derp_mesh_simplify's / derp_mesh_simplify_parallel's result (host): what the downloads return once one has run
   bool simplified = false;
   std::vector<double> sV;
   std::vector<int32_t> sF;
+  // derp_mesh_simplify_parallel's state besides V, F, planes, costs and vq, which it works on in place
+  DevBuf alive, boundary, vcount, vstart, vcursor, adj, keys, keysFeasible, keysSorted, vals, valsSorted, claim, wins, blockSum, blockOff,
+      counters, sortTemp, outV, outF;
+  std::vector<derp_mesh_pass> passes;  // of the last derp_mesh_simplify_parallel (derp_mesh_parallel_pass)
 };
 
 }  // namespace
@@ -2833,6 +2839,190 @@ int derp_mesh_simplify(derp_ctx* c, int num_faces_out, float strictness, int rem
   m.sV.resize(nv * 3);
   m.sF.resize(nf * 3);
   m.simplified = true;
+  return 0;
+}
+
+// rocPRIM's stable radix sort of (cost key, face * 3 + edge): Onesweep with 256 threads x 8 items (its default for
+// this pair of types spills to scratch memory), from 4096 items on, so that the tests' meshes take the path of
+// full-size ones
+namespace {
+using MeshSortConfig = rocprim::radix_sort_config<
+    rocprim::default_config, rocprim::default_config,
+    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<256, 12>, rocprim::kernel_config<256, 8>, 8>, 4096>;
+}
+
+// The pass-parallel simplifier (derp_mesh.h, "the pass-parallel simplifier"): the whole loop on the device, the host
+// reads one set of counters per pass.
+int derp_mesh_simplify_parallel(derp_ctx* c, int num_faces_out, float strictness, int remove_boundary_edges, int equi_error,
+                                int* stats) {
+  TRY(need_mesh(c));
+  MeshState& m = *c->mesh;
+  if (m.simplified) {
+    return fail(c, "derp_mesh_simplify_parallel: the mesh has been simplified already");
+  }
+  if (num_faces_out < 0) {
+    return fail(c, "derp_mesh_simplify_parallel: a negative face budget");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  m.passes.clear();
+  int passes = 0, reason = DERP_MESH_EXIT_BUDGET;
+  const size_t nf = m.nf, nv = m.nv, n3 = nf * 3;
+  long long aliveFaces = (long long)nf;
+  if (n3 >= (size_t)kMeshApplied) {
+    return fail(c, "derp_mesh_simplify_parallel: %zu faces are more than an edge rank holds", nf);
+  }
+  if (aliveFaces > num_faces_out) {
+    TRY(mesh_setup_dev(c, equi_error));
+    const int nbF = mesh_blocks(nf), nbV = mesh_blocks(nv), nbE = mesh_blocks(n3);
+    ALLOC(c, m.alive, nf);
+    ALLOC(c, m.boundary, nv);
+    ALLOC(c, m.vcount, nv * 4);
+    ALLOC(c, m.vstart, nv * 4);
+    ALLOC(c, m.vcursor, nv * 4);
+    ALLOC(c, m.adj, n3 * 4);
+    ALLOC(c, m.keys, n3 * 8);
+    ALLOC(c, m.keysFeasible, n3 * 8);
+    ALLOC(c, m.keysSorted, n3 * 8);
+    ALLOC(c, m.vals, n3 * 4);
+    ALLOC(c, m.valsSorted, n3 * 4);
+    ALLOC(c, m.claim, nf * 4);
+    ALLOC(c, m.wins, n3 * 4);
+    ALLOC(c, m.blockSum, (size_t)nbE * 4);
+    ALLOC(c, m.blockOff, (size_t)nbE * 8);
+    ALLOC(c, m.counters, (MESH_CNT_SLOTS + 1) * 8);
+    double* V = m.V.as<double>();
+    int32_t* F = m.F.as<int32_t>();
+    double *costs = m.costs.as<double>(), *vq = m.vq.as<double>();
+    const double* planes = m.planes.as<double>();
+    uint8_t *alive = m.alive.as<uint8_t>(), *boundary = m.boundary.as<uint8_t>();
+    uint32_t *claim = m.claim.as<uint32_t>(), *wins = m.wins.as<uint32_t>(), *blockSum = m.blockSum.as<uint32_t>();
+    unsigned long long *blockOff = m.blockOff.as<unsigned long long>(), *counters = m.counters.as<unsigned long long>();
+    const MeshAdjacency A = {m.vstart.as<uint32_t>(), m.vcount.as<uint32_t>(), m.adj.as<uint32_t>()};
+    const dim3 blk(kMeshBlock);
+    HIPCHK(c, hipMemsetAsync(alive, 1, nf, c->stream));
+    HIPCHK(c, hipMemsetAsync(boundary, 0, nv, c->stream));
+    while (aliveFaces > num_faces_out) {
+      if ((size_t)passes >= nf) {  // every pass with a candidate deletes a face
+        return fail(c, "derp_mesh_simplify_parallel: %d passes over %zu faces", passes, nf);
+      }
+      // adjacency of the alive faces
+      HIPCHK(c, hipMemsetAsync(m.vcount.p, 0, nv * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(counters, 0, MESH_CNT_SLOTS * 8, c->stream));
+      HIPCHK(c, hipMemsetAsync(claim, 0xff, nf * 4, c->stream));
+      hipLaunchKernelGGL(k_par_vertex_degrees, dim3(nbF), blk, 0, c->stream, F, alive, nf, m.vcount.as<uint32_t>());
+      hipLaunchKernelGGL(k_par_block_sums<uint32_t>, dim3(nbV), blk, 0, c->stream, m.vcount.as<uint32_t>(), nv, blockSum);
+      hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, blockSum, nbV, blockOff,
+                         counters + MESH_CNT_SLOTS);
+      hipLaunchKernelGGL(k_par_vertex_starts, dim3(nbV), blk, 0, c->stream, m.vcount.as<uint32_t>(), nv, blockOff,
+                         m.vstart.as<uint32_t>(), m.vcursor.as<uint32_t>());
+      hipLaunchKernelGGL(k_par_adjacency_fill, dim3(nbF), blk, 0, c->stream, F, alive, nf, m.vcursor.as<uint32_t>(),
+                         m.adj.as<uint32_t>());
+      if (passes == 0) {
+        hipLaunchKernelGGL(k_par_boundaries, dim3(nbE), blk, 0, c->stream, A, F, nf, boundary);
+      }
+      // feasible set, its order, claims, winners
+      hipLaunchKernelGGL(k_par_feasible, dim3(nbE), blk, 0, c->stream, A, V, F, alive, nf, planes, costs, vq, boundary,
+                         remove_boundary_edges, equi_error, m.keys.as<unsigned long long>(), blockSum);
+      hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, blockSum, nbE, blockOff,
+                         counters + MESH_CNT_FEASIBLE);
+      hipLaunchKernelGGL(k_par_feasible_compact, dim3(nbE), blk, 0, c->stream, m.keys.as<unsigned long long>(), n3, blockOff,
+                         m.keysFeasible.as<unsigned long long>(), m.vals.as<uint32_t>());
+      KCHECK(c);
+      unsigned long long feasible = 0;
+      TRY(download_sync(c, &feasible, counters + MESH_CNT_FEASIBLE, 8));
+      if (feasible == 0) {
+        reason = DERP_MESH_EXIT_NO_CANDIDATES;
+        break;
+      }
+      if (feasible > n3) {
+        return fail(c, "derp_mesh_simplify_parallel: %llu feasible edges of %zu", feasible, n3);
+      }
+      size_t tempBytes = 0;
+      HIPCHK(c, rocprim::radix_sort_pairs<MeshSortConfig>(nullptr, tempBytes, m.keysFeasible.as<unsigned long long>(),
+                                                          m.keysSorted.as<unsigned long long>(), m.vals.as<uint32_t>(),
+                                                          m.valsSorted.as<uint32_t>(), (size_t)feasible, 0, 64, c->stream));
+      ALLOC(c, m.sortTemp, std::max<size_t>(tempBytes, 8));
+      HIPCHK(c, rocprim::radix_sort_pairs<MeshSortConfig>(m.sortTemp.p, tempBytes, m.keysFeasible.as<unsigned long long>(),
+                                                          m.keysSorted.as<unsigned long long>(), m.vals.as<uint32_t>(),
+                                                          m.valsSorted.as<uint32_t>(), (size_t)feasible, 0, 64, c->stream));
+      const unsigned long long* skeys = m.keysSorted.as<unsigned long long>();
+      const uint32_t* svals = m.valsSorted.as<uint32_t>();
+      const int nbN = mesh_blocks((size_t)feasible);  // from here on one thread per feasible edge, by rank
+      hipLaunchKernelGGL(k_par_claim, dim3(nbN), blk, 0, c->stream, A, F, skeys, svals, strictness, counters, claim);
+      hipLaunchKernelGGL(k_par_winners, dim3(nbN), blk, 0, c->stream, A, F, skeys, svals, strictness, claim, counters, wins,
+                         blockSum);
+      // budget cut in key order, then the collapses
+      hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, blockSum, nbN, blockOff,
+                         counters + MESH_CNT_SLOTS);
+      hipLaunchKernelGGL(k_par_apply_vertices, dim3(nbN), blk, 0, c->stream, V, F, vq, boundary, equi_error, svals, blockOff,
+                         aliveFaces, (long long)num_faces_out, wins, counters);
+      hipLaunchKernelGGL(k_par_apply_faces, dim3(nbF), blk, 0, c->stream, V, F, alive, nf, vq, boundary, equi_error, svals, claim,
+                         wins, costs);
+      KCHECK(c);
+      unsigned long long cnt[MESH_CNT_SLOTS];
+      TRY(download_sync(c, cnt, counters, sizeof cnt));
+      if (cnt[MESH_CNT_DELETED] == 0 || cnt[MESH_CNT_DELETED] > (unsigned long long)aliveFaces) {
+        return fail(c, "derp_mesh_simplify_parallel: pass %d deleted %llu of %lld faces", passes, cnt[MESH_CNT_DELETED], aliveFaces);
+      }
+      derp_mesh_pass p;
+      p.faces = aliveFaces;
+      p.feasible = (long long)cnt[MESH_CNT_FEASIBLE];
+      p.winners = (long long)cnt[MESH_CNT_WINNERS];
+      p.applied = (long long)cnt[MESH_CNT_APPLIED];
+      p.deleted = (long long)cnt[MESH_CNT_DELETED];
+      p.threshold = mesh_key_cost(cnt[MESH_CNT_THRESHOLD]);
+      m.passes.push_back(p);
+      aliveFaces -= (long long)cnt[MESH_CNT_DELETED];
+      ++passes;
+    }
+    // createFinalMesh
+    uint8_t* used = m.used.as<uint8_t>();  // (grid-sized: at least nv bytes)
+    uint32_t* vmap = m.vmap.as<uint32_t>();
+    ALLOC(c, m.outV, std::max<size_t>(nv * 24, 8));
+    ALLOC(c, m.outF, std::max<size_t>(nf * 12, 8));
+    HIPCHK(c, hipMemsetAsync(used, 0, nv, c->stream));
+    hipLaunchKernelGGL(k_par_vertices_used, dim3(nbF), blk, 0, c->stream, F, alive, nf, used);
+    hipLaunchKernelGGL(k_par_block_sums<uint8_t>, dim3(nbV), blk, 0, c->stream, used, nv, blockSum);
+    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, blockSum, nbV, blockOff, counters);
+    hipLaunchKernelGGL(k_par_final_vertices, dim3(nbV), blk, 0, c->stream, V, used, nv, blockOff, vmap, m.outV.as<double>());
+    hipLaunchKernelGGL(k_par_block_sums<uint8_t>, dim3(nbF), blk, 0, c->stream, alive, nf, blockSum);
+    hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, blockSum, nbF, blockOff, counters + 1);
+    hipLaunchKernelGGL(k_par_final_faces, dim3(nbF), blk, 0, c->stream, F, alive, nf, blockOff, vmap, m.outF.as<int32_t>());
+    KCHECK(c);
+    unsigned long long out[2] = {0, 0};
+    TRY(download_sync(c, out, counters, sizeof out));
+    if (out[0] > nv || (long long)out[1] != aliveFaces) {
+      return fail(c, "derp_mesh_simplify_parallel: inconsistent result (%llu vertices, %llu faces, %lld alive)", out[0], out[1],
+                  aliveFaces);
+    }
+    m.sV.resize((size_t)out[0] * 3);
+    m.sF.resize((size_t)out[1] * 3);
+    if (out[0]) {
+      TRY(download_sync(c, m.sV.data(), m.outV.p, m.sV.size() * 8));
+    }
+    if (out[1]) {
+      TRY(download_sync(c, m.sF.data(), m.outF.p, m.sF.size() * 4));
+    }
+  } else {  // 0 passes: the mesh as built
+    m.sV.resize(nv * 3);
+    m.sF.resize(nf * 3);
+    TRY(derp_mesh_download_f64(c, m.sV.data(), m.sF.data()));
+  }
+  m.simplified = true;
+  if (stats) {
+    stats[0] = passes;
+    stats[1] = reason;
+  }
+  return 0;
+}
+
+int derp_mesh_parallel_pass(derp_ctx* c, int pass, derp_mesh_pass* out) {
+  TRY(need_mesh(c));
+  const MeshState& m = *c->mesh;
+  if (!out || pass < 0 || (size_t)pass >= m.passes.size()) {
+    return fail(c, "derp_mesh_parallel_pass: no pass %d (the last derp_mesh_simplify_parallel ran %zu)", pass, m.passes.size());
+  }
+  *out = m.passes[pass];
   return 0;
 }
 

@@ -346,4 +346,386 @@ __global__ void __launch_bounds__(kMeshBlock)
                                       false, equiError != 0, target);
 }
 
+
+// ---- the pass-parallel simplifier (derp_mesh_simplify_parallel) --------------------------------
+// MeshSimplifier's collapse arithmetic and rules (computeError, haveNormalsFlipped, commonFaces, updateCosts) with
+// another choice of what a pass collapses: the threshold is a rank over the feasible edges only, and the collapses of
+// a pass are the candidates that hold the smallest (cost, face, edge) key on every face they touch, so that no two of
+// them share a face and all of them can be applied at once. Faces keep their index in the built mesh; a deleted face
+// only loses its alive flag. A vertex's alive faces are a CSR list rebuilt every pass; its order is whatever the
+// atomics gave, and every use of it below is a minimum, an OR or a count.
+constexpr unsigned long long kMeshNoKey = ~0ull;  // (the pattern of a NaN: never a feasible cost)
+constexpr uint32_t kMeshNoClaim = 0xffffffffu;
+constexpr uint32_t kMeshApplied = 0x80000000u;
+// slots of the per-pass counters
+enum { MESH_CNT_FEASIBLE = 0, MESH_CNT_WINNERS, MESH_CNT_APPLIED, MESH_CNT_DELETED, MESH_CNT_THRESHOLD, MESH_CNT_SLOTS };
+
+// a cost as a 64-bit pattern whose unsigned order is the order of the doubles (-0 counts as +0)
+__host__ __device__ __forceinline__ unsigned long long mesh_cost_key(double c) {
+  c = c == 0 ? 0.0 : c;
+  unsigned long long b;
+  memcpy(&b, &c, 8);
+  return (b >> 63) ? ~b : b | 1ull << 63;
+}
+__host__ __device__ __forceinline__ double mesh_key_cost(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? k & ~(1ull << 63) : ~k;
+  double c;
+  memcpy(&c, &b, 8);
+  return c;
+}
+
+struct MeshAdjacency {  // faces [start[v], start[v] + count[v]) of adj are vertex v's alive faces
+  const uint32_t* __restrict__ start;
+  const uint32_t* __restrict__ count;
+  const uint32_t* __restrict__ adj;
+};
+
+__device__ __forceinline__ derp_mesh::V3 mesh_coord(const double* __restrict__ V, int v) {
+  return {V[3 * (size_t)v], V[3 * (size_t)v + 1], V[3 * (size_t)v + 2]};
+}
+__device__ __forceinline__ bool mesh_face_has(const int32_t* __restrict__ F, uint32_t f, int v) {
+  return F[3 * (size_t)f] == v || F[3 * (size_t)f + 1] == v || F[3 * (size_t)f + 2] == v;
+}
+// commonFaces(v0, v1).size(): a face is in both lists once, so it is the faces of v0 that hold v1
+__device__ __forceinline__ uint32_t mesh_common_faces(const MeshAdjacency& A, const int32_t* __restrict__ F, int v0, int v1) {
+  uint32_t n = 0;
+  const uint32_t s = A.start[v0], e = s + A.count[v0];
+  for (uint32_t k = s; k < e; ++k) {
+    n += mesh_face_has(F, A.adj[k], v1) ? 1u : 0u;
+  }
+  return n;
+}
+// computeError of the edge (v0, v1) as MeshSimplifier::computeError(v0, v1, target) calls it
+__device__ __forceinline__ double mesh_edge_error(const double* __restrict__ V, const double* __restrict__ vq,
+                                                  const uint8_t* __restrict__ boundary, int v0, int v1, bool equiError,
+                                                  derp_mesh::V3& target) {
+  return derp_mesh::compute_error(vq + (size_t)v0 * derp_mesh::kQuadric, vq + (size_t)v1 * derp_mesh::kQuadric,
+                                  mesh_coord(V, v0), mesh_coord(V, v1), boundary[v0] && boundary[v1], equiError, target);
+}
+// haveNormalsFlipped (MeshSimplifier.cpp:348-382) over the alive faces of v0, against the set-up's face normals
+__device__ __forceinline__ bool mesh_normals_flipped(const MeshAdjacency& A, const double* __restrict__ V,
+                                                     const int32_t* __restrict__ F, const double* __restrict__ planes,
+                                                     const derp_mesh::V3& p, int v0, int v1) {
+  const uint32_t s = A.start[v0], e = s + A.count[v0];
+  for (uint32_t k = s; k < e; ++k) {
+    const size_t t = A.adj[k];
+    const int a = F[3 * t], b = F[3 * t + 1], c = F[3 * t + 2];
+    // the two vertices after v0 in the face's order (order 0 when v0 is not found, as there)
+    const int i0 = a == v0 ? b : b == v0 ? c : c == v0 ? a : b;
+    const int i1 = a == v0 ? c : b == v0 ? a : c == v0 ? b : c;
+    if (i0 == v1 || i1 == v1) {
+      continue;
+    }
+    const derp_mesh::V3 d0 = derp_mesh::normalized(derp_mesh::sub(mesh_coord(V, i0), p));
+    const derp_mesh::V3 d1 = derp_mesh::normalized(derp_mesh::sub(mesh_coord(V, i1), p));
+    const derp_mesh::V3 normal = derp_mesh::normalized(derp_mesh::cross(d0, d1));
+    if (derp_mesh::dot(normal, {planes[4 * t], planes[4 * t + 1], planes[4 * t + 2]}) < 0) {
+      return true;
+    }
+  }
+  return false;
+}
+
+// ---- a pass's adjacency: count, scan, fill
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_vertex_degrees(const int32_t* __restrict__ F, const uint8_t* __restrict__ alive, size_t nf, uint32_t* __restrict__ count) {
+  const size_t f = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (f >= nf || !alive[f]) {
+    return;
+  }
+  for (int k = 0; k < 3; ++k) {
+    atomicAdd(&count[F[3 * f + k]], 1u);
+  }
+}
+// the sum of every block's values (counts or 0 / 1 flags), for k_scan_block_counts
+template <typename T>
+__global__ void __launch_bounds__(kMeshBlock) k_par_block_sums(const T* __restrict__ values, size_t n, uint32_t* __restrict__ blockSum) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t i = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  uint32_t total;
+  mesh_block_scan(i < n ? (uint32_t)values[i] : 0u, waveTotal, total);
+  if (threadIdx.x == 0) {
+    blockSum[blockIdx.x] = total;
+  }
+}
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_vertex_starts(const uint32_t* __restrict__ count, size_t nv, const unsigned long long* __restrict__ blockOffset,
+                        uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t v = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  uint32_t total;
+  const uint32_t rank = mesh_block_scan(v < nv ? count[v] : 0u, waveTotal, total);
+  if (v < nv) {
+    start[v] = cursor[v] = (uint32_t)blockOffset[blockIdx.x] + rank;
+  }
+}
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_adjacency_fill(const int32_t* __restrict__ F, const uint8_t* __restrict__ alive, size_t nf, uint32_t* __restrict__ cursor,
+                         uint32_t* __restrict__ adj) {
+  const size_t f = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (f >= nf || !alive[f]) {
+    return;
+  }
+  for (int k = 0; k < 3; ++k) {
+    adj[atomicAdd(&cursor[F[3 * f + k]], 1u)] = (uint32_t)f;
+  }
+}
+
+// identifyBoundaries' set, before the first pass: both ends of every edge with exactly one common face
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_boundaries(MeshAdjacency A, const int32_t* __restrict__ F, size_t nf, uint8_t* __restrict__ boundary) {
+  const size_t e = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (e >= nf * 3) {
+    return;
+  }
+  const size_t f = e / 3;
+  const int i = (int)(e % 3);
+  const int v0 = F[3 * f + i], v1 = F[3 * f + (i + 1) % 3];
+  if (mesh_common_faces(A, F, v0, v1) == 1) {
+    boundary[v0] = 1;
+    boundary[v1] = 1;
+  }
+}
+
+// ---- the feasible set: one thread per (face, edge) -> its sort key (kMeshNoKey when barred), and every block's count
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_feasible(MeshAdjacency A, const double* __restrict__ V, const int32_t* __restrict__ F, const uint8_t* __restrict__ alive,
+                   size_t nf, const double* __restrict__ planes, const double* __restrict__ costs, const double* __restrict__ vq,
+                   const uint8_t* __restrict__ boundary, int removeBoundaryEdges, int equiError, unsigned long long* __restrict__ keys,
+                   uint32_t* __restrict__ blockSum) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t e = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  unsigned long long key = kMeshNoKey;
+  if (e < nf * 3 && alive[e / 3]) {
+    const size_t f = e / 3;
+    const int i = (int)(e % 3);
+    const int v0 = F[3 * f + i], v1 = F[3 * f + (i + 1) % 3];
+    const bool b0 = boundary[v0] != 0, b1 = boundary[v1] != 0;
+    const double cost = costs[e];
+    if (b0 == b1 && (removeBoundaryEdges || !(b0 || b1)) && cost == cost) {
+      derp_mesh::V3 target;
+      mesh_edge_error(V, vq, boundary, v0, v1, equiError != 0, target);
+      if (!mesh_normals_flipped(A, V, F, planes, target, v0, v1) && !mesh_normals_flipped(A, V, F, planes, target, v1, v0)) {
+        key = mesh_cost_key(cost);
+      }
+    }
+  }
+  if (e < nf * 3) {
+    keys[e] = key;
+  }
+  uint32_t total;
+  mesh_block_scan(key != kMeshNoKey ? 1u : 0u, waveTotal, total);
+  if (threadIdx.x == 0) {
+    blockSum[blockIdx.x] = total;
+  }
+}
+// the feasible edges alone, by ascending face * 3 + edge: what the sort reads
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_feasible_compact(const unsigned long long* __restrict__ keys, size_t n3, const unsigned long long* __restrict__ blockOffset,
+                           unsigned long long* __restrict__ ckeys, uint32_t* __restrict__ cvals) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t e = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const unsigned long long key = e < n3 ? keys[e] : kMeshNoKey;
+  uint32_t total;
+  const uint32_t rank = mesh_block_scan(key != kMeshNoKey ? 1u : 0u, waveTotal, total);
+  if (key != kMeshNoKey) {
+    const size_t o = (size_t)blockOffset[blockIdx.x] + rank;
+    ckeys[o] = key;
+    cvals[o] = (uint32_t)e;
+  }
+}
+
+// The sorted keys are the feasible edges in (cost, face * 3 + edge) order (a stable sort of keys that went in by
+// ascending index), so an edge's position r is its rank. getThreshold's index over them:
+__device__ __forceinline__ unsigned long long mesh_threshold_key(const unsigned long long* __restrict__ skeys, unsigned long long n,
+                                                               float strictness) {
+  return skeys[(int)(strictness * (float)(n - 1))];
+}
+// claim: every candidate writes its rank to each face it touches; the smallest stays
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_claim(MeshAdjacency A, const int32_t* __restrict__ F, const unsigned long long* __restrict__ skeys,
+                const uint32_t* __restrict__ svals, float strictness, unsigned long long* __restrict__ counters,
+                uint32_t* __restrict__ claim) {
+  const size_t r = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const unsigned long long n = counters[MESH_CNT_FEASIBLE];
+  if (r >= n) {
+    return;
+  }
+  const unsigned long long threshold = mesh_threshold_key(skeys, n, strictness);
+  if (r == 0) {
+    counters[MESH_CNT_THRESHOLD] = threshold;
+  }
+  if (skeys[r] > threshold) {
+    return;
+  }
+  const size_t f = svals[r] / 3;
+  const int i = (int)(svals[r] % 3);
+  const int v[2] = {F[3 * f + i], F[3 * f + (i + 1) % 3]};
+  for (int side = 0; side < 2; ++side) {
+    const uint32_t s = A.start[v[side]], e = s + A.count[v[side]];
+    for (uint32_t k = s; k < e; ++k) {
+      atomicMin(&claim[A.adj[k]], (uint32_t)r);
+    }
+  }
+}
+// winners: the candidates that kept every face they touch -> wins[r] = commonFaces(v0, v1).size() (0: no winner), and
+// every block's sum of them for the prefix sums of the budget cut
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_winners(MeshAdjacency A, const int32_t* __restrict__ F, const unsigned long long* __restrict__ skeys,
+                  const uint32_t* __restrict__ svals, float strictness, const uint32_t* __restrict__ claim,
+                  unsigned long long* __restrict__ counters, uint32_t* __restrict__ wins, uint32_t* __restrict__ blockSum) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t r = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const unsigned long long n = counters[MESH_CNT_FEASIBLE];
+  uint32_t common = 0;
+  if (r < n && skeys[r] <= mesh_threshold_key(skeys, n, strictness)) {
+    const size_t f = svals[r] / 3;
+    const int i = (int)(svals[r] % 3);
+    const int v[2] = {F[3 * f + i], F[3 * f + (i + 1) % 3]};
+    bool won = true;
+    for (int side = 0; side < 2; ++side) {
+      const uint32_t s = A.start[v[side]], e = s + A.count[v[side]];
+      for (uint32_t k = s; k < e; ++k) {
+        won = won && claim[A.adj[k]] == (uint32_t)r;
+      }
+    }
+    if (won) {
+      common = mesh_common_faces(A, F, v[0], v[1]);
+    }
+  }
+  if (r < n) {
+    wins[r] = common;
+  }
+  const unsigned long long ballot = __ballot(common != 0);
+  if ((threadIdx.x & 63) == 0 && ballot) {
+    atomicAdd(&counters[MESH_CNT_WINNERS], (unsigned long long)__popcll(ballot));
+  }
+  uint32_t total;
+  mesh_block_scan(common, waveTotal, total);
+  if (threadIdx.x == 0) {
+    blockSum[blockIdx.x] = total;
+  }
+}
+
+// The budget cut and updateCosts' vertex half: a winner is applied while the faces alive before the pass, less those
+// the winners before it (in key order) delete, exceed the budget. v0 takes the target and q0 + q1. No other winner
+// reads or writes v0 or v1: they are vertices of faces that only this winner touches.
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_apply_vertices(double* __restrict__ V, const int32_t* __restrict__ F, double* __restrict__ vq,
+                         const uint8_t* __restrict__ boundary, int equiError, const uint32_t* __restrict__ svals,
+                         const unsigned long long* __restrict__ blockOffset, long long aliveFaces, long long numFacesOut,
+                         uint32_t* __restrict__ wins, unsigned long long* __restrict__ counters) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t r = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const uint32_t common = r < counters[MESH_CNT_FEASIBLE] ? wins[r] : 0u;
+  uint32_t total;
+  const unsigned long long before = blockOffset[blockIdx.x] + mesh_block_scan(common, waveTotal, total);
+  if (common == 0 || !(aliveFaces - (long long)before > numFacesOut)) {
+    return;
+  }
+  const size_t f = svals[r] / 3;
+  const int i = (int)(svals[r] % 3);
+  const int v0 = F[3 * f + i], v1 = F[3 * f + (i + 1) % 3];
+  derp_mesh::V3 target;
+  mesh_edge_error(V, vq, boundary, v0, v1, equiError != 0, target);
+  V[3 * (size_t)v0] = target.x;
+  V[3 * (size_t)v0 + 1] = target.y;
+  V[3 * (size_t)v0 + 2] = target.z;
+  for (int k = 0; k < derp_mesh::kQuadric; ++k) {
+    vq[(size_t)v0 * derp_mesh::kQuadric + k] = vq[(size_t)v0 * derp_mesh::kQuadric + k] + vq[(size_t)v1 * derp_mesh::kQuadric + k];
+  }
+  wins[r] = common | kMeshApplied;
+  atomicAdd(&counters[MESH_CNT_APPLIED], 1ull);
+  atomicAdd(&counters[MESH_CNT_DELETED], (unsigned long long)common);
+}
+// ... and its face half, one thread per face: a face claimed by an applied winner is deleted when it holds both ends
+// of the edge (commonFaces); otherwise its first v0 or v1 becomes v0 and its three costs are computed again. The
+// winner's own face holds both ends, so nothing rewrites the indices read through svals here.
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_apply_faces(const double* __restrict__ V, int32_t* __restrict__ F, uint8_t* __restrict__ alive, size_t nf,
+                      const double* __restrict__ vq, const uint8_t* __restrict__ boundary, int equiError,
+                      const uint32_t* __restrict__ svals, const uint32_t* __restrict__ claim, const uint32_t* __restrict__ wins,
+                      double* __restrict__ costs) {
+  const size_t f = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (f >= nf || !alive[f]) {
+    return;
+  }
+  const uint32_t r = claim[f];
+  if (r == kMeshNoClaim || !(wins[r] & kMeshApplied)) {
+    return;
+  }
+  const size_t wf = svals[r] / 3;
+  const int wi = (int)(svals[r] % 3);
+  const int v0 = F[3 * wf + wi], v1 = F[3 * wf + (wi + 1) % 3];
+  int a = F[3 * f], b = F[3 * f + 1], c = F[3 * f + 2];
+  const bool has0 = a == v0 || b == v0 || c == v0, has1 = a == v1 || b == v1 || c == v1;
+  if (has0 && has1) {
+    alive[f] = 0;
+    return;
+  }
+  if (a == v0 || a == v1) {
+    a = v0;
+  } else if (b == v0 || b == v1) {
+    b = v0;
+  } else if (c == v0 || c == v1) {
+    c = v0;
+  }
+  F[3 * f] = a;
+  F[3 * f + 1] = b;
+  F[3 * f + 2] = c;
+  // one copy of computeError, three turns (three inlined copies spill to scratch memory)
+#pragma unroll 1
+  for (int k = 0; k < 3; ++k) {
+    derp_mesh::V3 target;
+    costs[3 * f + k] = mesh_edge_error(V, vq, boundary, a, b, equiError != 0, target);
+    const int first = a;
+    a = b;
+    b = c;
+    c = first;
+  }
+}
+
+// ---- createFinalMesh: faces in their original order, the vertices they use ascending
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_vertices_used(const int32_t* __restrict__ F, const uint8_t* __restrict__ alive, size_t nf, uint8_t* __restrict__ used) {
+  const size_t f = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (f >= nf || !alive[f]) {
+    return;
+  }
+  for (int k = 0; k < 3; ++k) {
+    used[F[3 * f + k]] = 1;
+  }
+}
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_final_vertices(const double* __restrict__ V, const uint8_t* __restrict__ used, size_t nv,
+                         const unsigned long long* __restrict__ blockOffset, uint32_t* __restrict__ vmap, double* __restrict__ outV) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t v = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const bool u = v < nv && used[v];
+  uint32_t total;
+  const uint32_t rank = mesh_block_scan(u ? 1u : 0u, waveTotal, total);
+  if (u) {
+    const size_t o = (size_t)blockOffset[blockIdx.x] + rank;
+    vmap[v] = (uint32_t)o;
+    outV[3 * o] = V[3 * v];
+    outV[3 * o + 1] = V[3 * v + 1];
+    outV[3 * o + 2] = V[3 * v + 2];
+  }
+}
+__global__ void __launch_bounds__(kMeshBlock)
+    k_par_final_faces(const int32_t* __restrict__ F, const uint8_t* __restrict__ alive, size_t nf,
+                      const unsigned long long* __restrict__ blockOffset, const uint32_t* __restrict__ vmap, int32_t* __restrict__ outF) {
+  __shared__ uint32_t waveTotal[kMeshBlock / 64];
+  const size_t f = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  const bool u = f < nf && alive[f];
+  uint32_t total;
+  const uint32_t rank = mesh_block_scan(u ? 1u : 0u, waveTotal, total);
+  if (u) {
+    const size_t o = (size_t)blockOffset[blockIdx.x] + rank;
+    for (int k = 0; k < 3; ++k) {
+      outF[3 * o + k] = (int32_t)vmap[F[3 * f + k]];
+    }
+  }
+}
+
 }  // namespace derp

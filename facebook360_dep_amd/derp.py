@@ -46,6 +46,11 @@ class Options(C.Structure):
     ]
 
 
+class MeshPass(C.Structure):  # derp_mesh_pass
+    _fields_ = [("faces", C.c_longlong), ("feasible", C.c_longlong), ("winners", C.c_longlong), ("applied", C.c_longlong),
+                ("deleted", C.c_longlong), ("threshold", C.c_double)]
+
+
 class RenderParams(C.Structure):
     """derp_render_params (include/derp_hip.h): one SimpleMeshRenderer view."""
     _fields_ = [
@@ -104,6 +109,7 @@ EXPORTS = [
     "derp_render_vertices",
     "derp_export_points", "derp_points_begin", "derp_points_splat", "derp_points_download", "derp_project_equirect_mask",
     "derp_mesh_build", "derp_mesh_counts", "derp_mesh_setup", "derp_mesh_simplify", "derp_mesh_download_f64", "derp_mesh_download",
+    "derp_mesh_simplify_parallel", "derp_mesh_parallel_pass",
     "derp_mesh_setup_host", "derp_mesh_simplify_host",
     "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
     "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
@@ -593,6 +599,19 @@ class Derp:
         self._ck(lib().derp_mesh_simplify(self.h, num_faces_out, C.c_float(strictness), int(remove_boundary_edges),
                                           int(equi_error), int(host_setup), stats))
         return stats[0], stats[1]
+
+    def mesh_simplify_parallel(self, num_faces_out, strictness=0.2, remove_boundary_edges=False, equi_error=True):
+        """the pass-parallel simplifier of the built mesh, on the device -> (passes, DERP_MESH_EXIT_*)"""
+        stats = (C.c_int * 2)()
+        self._ck(lib().derp_mesh_simplify_parallel(self.h, num_faces_out, C.c_float(strictness), int(remove_boundary_edges),
+                                                   int(equi_error), stats))
+        return stats[0], stats[1]
+
+    def mesh_parallel_pass(self, index):
+        """-> (alive faces before, feasible edges, winners, winners applied, faces deleted, threshold) of pass `index`"""
+        p = MeshPass()
+        self._ck(lib().derp_mesh_parallel_pass(self.h, index, C.byref(p)))
+        return p.faces, p.feasible, p.winners, p.applied, p.deleted, p.threshold
 
     def mesh_download_f64(self):
         nv, nf, _ = self.mesh_counts()

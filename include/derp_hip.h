@@ -302,7 +302,7 @@ int derp_project_equirect_mask(derp_ctx* ctx, int cam, const uint8_t* eqr, int e
  *   mesh_util::applyMaskToVertexesAndFaces (:345-405). `resolution` (double[2], NULL: as the rig file holds it) is
  *   what resizeRig hands Camera::rescale (:318-339). Camera::getScalarFocal's focal.x == -focal.y is checked here.
  *   The context holds one mesh: the one built last.
- * derp_mesh_counts: vertices and faces of the mesh (after derp_mesh_simplify: of its result), and the faces getFaces
+ * derp_mesh_counts: vertices and faces of the mesh (after a simplify: of its result), and the faces getFaces
  *   made before the mask removed any (the "Removed N of M faces" line, :191-198).
  * derp_mesh_setup: MeshSimplifier::computeInitialQuadrics (MeshSimplifier.cpp:182-239) of the built mesh on the
  *   device: face_planes [faces][4] (Face::normal and -normal.p0), edge_costs [faces][3] (Face::cost), vertex_quadrics
@@ -311,16 +311,43 @@ int derp_project_equirect_mask(derp_ctx* ctx, int cam, const uint8_t* eqr, int e
  *   remove_boundary_edges) (:456-562) of the built mesh: the set-up on the device (host_setup = 0) or on the host, the
  *   collapse loop on the host (derp_mesh_simplify_host). stats (int[2], may be NULL): passes of the loop, and how it
  *   ended (DERP_MESH_EXIT_*).
+ * derp_mesh_simplify_parallel: a second simplifier of the built mesh, set-up and loop on the device, with the same
+ *   preconditions, refusals and stats. The reference's: the set-up, computeError and its target, haveNormalsFlipped
+ *   against the set-up's face normals, the boundary vertices of identifyBoundaries (found once), commonFaces,
+ *   updateCosts, createFinalMesh. Not the reference's: what a pass collapses. Feasible edges = those the reference
+ *   would not bar (equal boundary flags, no boundary vertex unless remove_boundary_edges, a cost that is no NaN, no
+ *   flipped normal on either side); the threshold is getThreshold's rank int(strictness * float(n - 1)) over the n
+ *   feasible costs alone; of the feasible edges at or under it, those with the smallest (cost, face, edge) on every
+ *   alive face of their two vertices are collapsed together, in that order while the faces left exceed
+ *   num_faces_out. The loop ends when they do not (DERP_MESH_EXIT_BUDGET) or no edge is feasible
+ *   (DERP_MESH_EXIT_NO_CANDIDATES). Results are the same from run to run, and differ from derp_mesh_simplify's.
+ * derp_mesh_parallel_pass: what pass `pass` (0 .. passes - 1) of the last derp_mesh_simplify_parallel saw.
  * derp_mesh_download_f64 / derp_mesh_download: MeshSimplifier::getVertexes / getFaces, or the built mesh when it was
  *   not simplified; the second as mesh_util::writeDepth lays the files out (MeshUtil.h:72-89): float32 x y z rows and
  *   uint32 index triples, with z < 0 raised to FLT_MIN first when clamp_negative_z (ConvertToBinary.cpp:211-217). */
-enum { DERP_MESH_EXIT_BUDGET = 0, DERP_MESH_EXIT_INFINITE_THRESHOLD = 1, DERP_MESH_EXIT_STUCK = 2 };
+enum {
+  DERP_MESH_EXIT_BUDGET = 0,
+  DERP_MESH_EXIT_INFINITE_THRESHOLD = 1,
+  DERP_MESH_EXIT_STUCK = 2,
+  DERP_MESH_EXIT_NO_CANDIDATES = 3
+};
+typedef struct derp_mesh_pass {
+  long long faces;     /* alive before the pass */
+  long long feasible;  /* feasible edges */
+  long long winners;   /* candidates that held every face they touch */
+  long long applied;   /* winners collapsed (all of them except in a pass cut at the budget) */
+  long long deleted;   /* faces the pass deleted */
+  double threshold;
+} derp_mesh_pass;
 int derp_mesh_build(derp_ctx* ctx, int cam, const float* disparity, int w, int h, const double* resolution,
                     double depth_scale, const uint8_t* mask, int mask_w, int mask_h, float tear_ratio);
 int derp_mesh_counts(derp_ctx* ctx, size_t* vertices, size_t* faces, size_t* faces_unmasked);
 int derp_mesh_setup(derp_ctx* ctx, int equi_error, double* face_planes, double* edge_costs, double* vertex_quadrics);
 int derp_mesh_simplify(derp_ctx* ctx, int num_faces_out, float strictness, int remove_boundary_edges, int equi_error,
                        int host_setup, int* stats);
+int derp_mesh_simplify_parallel(derp_ctx* ctx, int num_faces_out, float strictness, int remove_boundary_edges,
+                                int equi_error, int* stats);
+int derp_mesh_parallel_pass(derp_ctx* ctx, int pass, derp_mesh_pass* out);
 int derp_mesh_download_f64(derp_ctx* ctx, double* vertices, int32_t* faces);
 int derp_mesh_download(derp_ctx* ctx, int clamp_negative_z, float* vtx, uint32_t* idx);
 /* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
