@@ -3568,3 +3568,4 @@ int derp_render_format(derp_ctx* c, const char* format, const derp_render_params
 }  // extern "C"
 
 #include "derp_sequence.h"
+#include "derp_isp.h"

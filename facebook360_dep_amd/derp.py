@@ -123,6 +123,8 @@ EXPORTS = [
     "derp_seq_host_inputs", "derp_seq_buffer_copy", "derp_seq_upload_color_plane", "derp_seq_upload_disparity", "derp_seq_download_disparity", "derp_seq_exchange_inputs_level",
     "derp_seq_level_compute_frame", "derp_seq_level_provided_frame", "derp_seq_mark_exchanged", "derp_seq_level_filter_frame", "derp_seq_download_filtered",
     "derp_seq_run", "derp_seq_stats", "derp_seq_stats_reset", "derp_seq_exchange_exposed_ms",
+    "derp_isp_config_default", "derp_isp_create", "derp_isp_destroy", "derp_isp_output_size", "derp_isp_process",
+    "derp_isp_stage", "derp_isp_tables",
 ]
 
 _lib = None
@@ -805,3 +807,120 @@ def average_score(score, mask):
 def format_results(avg):
     """rephoto_util::formatResults (RephotographyUtil.h:110-116)."""
     return "R %.2f%%, G %.2f%%, B %.2f%%" % (100 * avg[2], 100 * avg[1], 100 * avg[0])
+
+
+# ---------------------------------------------------------------- camera ISP (raw Bayer -> RGB)
+ISP_MAX_ROLLOFF = 16
+ISP_FILTERS = {"bilinear": 0, "frequency": 1, "edge_aware": 2, "chroma_suppressed_bilinear": 3}
+ISP_STAGES = ["load", "pixel", "stuck", "demosaic", "color", "lowpass", "sharpened"]
+
+
+class IspConfig(C.Structure):
+    """derp_isp_config (include/derp_hip.h)."""
+    _fields_ = [
+        ("bits_per_pixel", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("is_little_endian", C.c_int32),
+        ("is_row_major", C.c_int32), ("bayer_pattern", C.c_char * 8), ("plane_order", C.c_char * 8),
+        ("black_level", C.c_float * 3), ("clamp_min", C.c_float * 3), ("clamp_max", C.c_float * 3),
+        ("stuck_pixel_threshold", C.c_int32), ("stuck_pixel_darkness_threshold", C.c_float),
+        ("stuck_pixel_radius", C.c_int32), ("n_rolloff_h", C.c_int32), ("n_rolloff_v", C.c_int32),
+        ("rolloff_h", (C.c_float * 3) * ISP_MAX_ROLLOFF), ("rolloff_v", (C.c_float * 3) * ISP_MAX_ROLLOFF),
+        ("white_balance_gain", C.c_float * 3), ("ccm", C.c_float * 9), ("saturation", C.c_float), ("gamma", C.c_float * 3),
+        ("low_key_boost", C.c_float * 3), ("high_key_boost", C.c_float * 3), ("contrast", C.c_float),
+        ("sharpening", C.c_float * 3), ("sharpening_support", C.c_float), ("noise_core", C.c_float),
+        ("n_companding_lut", C.c_int32),
+    ]
+
+
+def isp_config(config):
+    """The "CameraIsp" object of an isp.json (or the whole file's dict) -> derp_isp_config; missing keys keep the
+    reference's defaults (CameraIsp.h:490-562)."""
+    k = IspConfig()
+    lib().derp_isp_config_default(C.byref(k))
+    j = config.get("CameraIsp", config) if config else {}
+    for key, field in (("bitsPerPixel", "bits_per_pixel"), ("width", "width"), ("height", "height"),
+                       ("stuckPixelThreshold", "stuck_pixel_threshold"), ("stuckPixelRadius", "stuck_pixel_radius")):
+        if key in j:
+            setattr(k, field, int(j[key]))
+    for key, field in (("isLittleEndian", "is_little_endian"), ("isRowMajor", "is_row_major")):
+        if key in j:
+            setattr(k, field, int(bool(j[key])))
+    for key, field in (("bayerPattern", "bayer_pattern"), ("planeOrder", "plane_order")):
+        if key in j:
+            setattr(k, field, j[key].upper().encode())
+    for key, field in (("stuckPixelDarknessThreshold", "stuck_pixel_darkness_threshold"), ("saturation", "saturation"),
+                       ("contrast", "contrast"), ("sharpeningSupport", "sharpening_support"), ("noiseCore", "noise_core")):
+        if key in j:
+            setattr(k, field, float(j[key]))
+    for key, field in (("blackLevel", "black_level"), ("clampMin", "clamp_min"), ("clampMax", "clamp_max"),
+                       ("whiteBalanceGain", "white_balance_gain"), ("gamma", "gamma"), ("lowKeyBoost", "low_key_boost"),
+                       ("highKeyBoost", "high_key_boost"), ("sharpening", "sharpening")):
+        if j.get(key) is not None:
+            for i in range(3):
+                getattr(k, field)[i] = float(j[key][i])
+    for key, field, count in (("vignetteRollOffH", "rolloff_h", "n_rolloff_h"), ("vignetteRollOffV", "rolloff_v", "n_rolloff_v")):
+        if j.get(key) is not None:
+            if len(j[key]) > ISP_MAX_ROLLOFF:
+                raise DerpError("%s holds more than %d points" % (key, ISP_MAX_ROLLOFF))
+            setattr(k, count, len(j[key]))
+            for n, p in enumerate(j[key]):
+                for i in range(3):
+                    getattr(k, field)[n][i] = float(p[i])
+    if j.get("ccm") is not None:
+        for r in range(3):
+            for c in range(3):
+                k.ccm[3 * r + c] = float(j["ccm"][r][c])
+    if j.get("compandingLut") is not None:
+        k.n_companding_lut = len(j["compandingLut"])
+    return k
+
+
+class Isp:
+    """One camera ISP (derp_isp_create .. derp_isp_destroy): CameraIsp of the reference, on the GPU."""
+
+    def __init__(self, config, demosaic_filter=0, pow2_downscale=1, apply_tone_curve=True, device=0):
+        self.cfg = config if isinstance(config, IspConfig) else isp_config(config)
+        h = C.c_void_p()
+        if lib().derp_isp_create(C.byref(h), device, C.byref(self.cfg), int(demosaic_filter), int(pow2_downscale),
+                                 int(bool(apply_tone_curve))):
+            raise DerpError(lib().derp_last_error(None).decode())
+        self.h = h
+        w, hh = C.c_int(), C.c_int()
+        self._ck(lib().derp_isp_output_size(self.h, C.byref(w), C.byref(hh)))
+        self.width, self.height = w.value, hh.value
+        self.dtype = np.uint8 if self.cfg.bits_per_pixel == 8 else np.uint16
+
+    def _ck(self, rc):
+        if rc:
+            raise DerpError(lib().derp_last_error(None).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().derp_isp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def process(self, raw):
+        """raw: the .raw file's bytes (or an array of them) -> [h, w, 3] BGR, u8 or u16 like the sensor"""
+        buf = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+        out = np.zeros((self.height, self.width, 3), self.dtype)
+        self._ck(lib().derp_isp_process(self.h, _p(buf), C.c_size_t(buf.size), _p(out)))
+        return out
+
+    def stage(self, stage):
+        """the fp32 result of a stage of the last process(): [h, w] (load, pixel, stuck) or [3, h, w] R, G, B"""
+        s = ISP_STAGES.index(stage) if isinstance(stage, str) else int(stage)
+        out = np.zeros((self.height, self.width) if s < 3 else (3, self.height, self.width), np.float32)
+        self._ck(lib().derp_isp_stage(self.h, s, _p(out)))
+        return out
+
+    def tables(self):
+        """-> (vignette_h [w, 3], vignette_v [h, 3], composite ccm [3, 3], tone lut [4096, 3]), as built on the host"""
+        vh, vv = np.zeros((self.width, 3), np.float32), np.zeros((self.height, 3), np.float32)
+        ccm, lut = np.zeros((3, 3), np.float32), np.zeros((4096, 3), np.float32)
+        self._ck(lib().derp_isp_tables(self.h, _p(vh), _p(vv), _p(ccm), _p(lut)))
+        return vh, vv, ccm, lut

@@ -504,6 +504,67 @@ int derp_seq_stats_reset(derp_seq* seq);
  * stream beside the filter of the owned frames whose windows hold no halo frame (reset by derp_seq_stats_reset) */
 int derp_seq_exchange_exposed_ms(derp_seq* seq, double* exposed_ms);
 
+/* ---- camera ISP: raw Bayer -> RGB (source/isp/CameraIsp.h, RawToRgb.cpp, RawUtil.cpp) ---------------
+ * The ISP has no rig, so it has a handle of its own. Errors of every derp_isp_* call (creation included) are
+ * left, per thread, where derp_last_error(NULL) reads them. */
+typedef struct derp_isp derp_isp;
+enum { DERP_ISP_MAX_ROLLOFF = 16 };
+enum { DERP_ISP_BILINEAR = 0, DERP_ISP_FREQUENCY = 1, DERP_ISP_EDGE_AWARE = 2, DERP_ISP_CHROMA_SUPPRESSED = 3 };
+enum {
+  DERP_ISP_STAGE_LOAD = 0,        /* loadImageFromSensor + resizeInput: 1 plane [h][w] */
+  DERP_ISP_STAGE_PIXEL = 1,       /* blackLevelAdjust, antiVignette, whiteBalance, clampAndStretch: 1 plane */
+  DERP_ISP_STAGE_STUCK = 2,       /* removeStuckPixels (the plane of stage 1 when stuckPixelRadius is 0): 1 plane */
+  DERP_ISP_STAGE_DEMOSAIC = 3,    /* demosaic: 3 planes R, G, B, each [h][w] */
+  DERP_ISP_STAGE_COLOR = 4,       /* colorCorrect: 3 planes */
+  DERP_ISP_STAGE_LOWPASS = 5,     /* iirLowPass (only when sharpening runs): 3 planes */
+  DERP_ISP_STAGE_SHARPENED = 6    /* sharpenWithIirLowPass (only when sharpening runs): 3 planes */
+};
+/* every field of the "CameraIsp" JSON object (CameraIsp.h:521-562); points are x, y, z = r, g, b */
+typedef struct {
+  int32_t bits_per_pixel;         /* "bitsPerPixel"  16 */
+  int32_t width, height;          /* "width", "height": the sensor's, 0 until set */
+  int32_t is_little_endian;       /* "isLittleEndian"  0 */
+  int32_t is_row_major;           /* "isRowMajor"  1 */
+  char bayer_pattern[8];          /* "bayerPattern"  "GBRG" (upper case) */
+  char plane_order[8];            /* "planeOrder"  "": interleaved */
+  float black_level[3];           /* "blackLevel"  0 */
+  float clamp_min[3];             /* "clampMin"  0 */
+  float clamp_max[3];             /* "clampMax"  1 */
+  int32_t stuck_pixel_threshold;  /* "stuckPixelThreshold"  0 */
+  float stuck_pixel_darkness_threshold; /* "stuckPixelDarknessThreshold"  0 */
+  int32_t stuck_pixel_radius;     /* "stuckPixelRadius"  0 = off */
+  int32_t n_rolloff_h, n_rolloff_v;  /* "vignetteRollOffH" / "vignetteRollOffV": one point (1, 1, 1) each */
+  float rolloff_h[DERP_ISP_MAX_ROLLOFF][3];
+  float rolloff_v[DERP_ISP_MAX_ROLLOFF][3];
+  float white_balance_gain[3];    /* "whiteBalanceGain"  1 */
+  float ccm[9];                   /* "ccm"  identity, row major */
+  float saturation;               /* "saturation"  1 */
+  float gamma[3];                 /* "gamma"  1 */
+  float low_key_boost[3];         /* "lowKeyBoost"  0 */
+  float high_key_boost[3];        /* "highKeyBoost"  0 */
+  float contrast;                 /* "contrast"  1 */
+  float sharpening[3];            /* "sharpening"  0: runs only when all three are non-zero */
+  float sharpening_support;       /* "sharpeningSupport"  10 / 2048 */
+  float noise_core;               /* "noiseCore"  1000 */
+  int32_t n_companding_lut;       /* "compandingLut": parsed and, as in the reference, never used */
+} derp_isp_config;
+void derp_isp_config_default(derp_isp_config* cfg);   /* CameraIsp::CameraIsp, CameraIsp.h:490-519 */
+/* cameraIspFromConfigFileWithOptions (RawUtil.cpp:42-57): setup(), setResize, setDemosaicFilter, setToneCurveEnabled.
+ * Refused before any allocation: a filter outside 0..3, DERP_ISP_FREQUENCY, a downscale other than 1, 2, 4, 8, odd or
+ * zero sensor dimensions, bits_per_pixel other than 8 or 16. Fails without a HIP device: there is no CPU path. */
+int derp_isp_create(derp_isp** out, int device, const derp_isp_config* cfg, int demosaic_filter, int pow2_downscale,
+                    int apply_tone_curve);
+void derp_isp_destroy(derp_isp* isp);
+int derp_isp_output_size(const derp_isp* isp, int* width, int* height);   /* getOutputWidth / getOutputHeight */
+/* rawToRgb (RawUtil.cpp:59-63): loadImageFromSensor + getImage<T>. `raw` is the file's content, raw_bytes >=
+ * width * height * bits_per_pixel / 8; out_bgr is [h][w][3] BGR, u8 or u16 like the sensor. */
+int derp_isp_process(derp_isp* isp, const void* raw, size_t raw_bytes, void* out_bgr);
+/* the fp32 plane(s) the last derp_isp_process left after a stage (tests) */
+int derp_isp_stage(derp_isp* isp, int stage, float* out);
+/* the host-built tables: curveHAtPixel [w][3] and curveVAtPixel [h][3] (CameraIsp.h:668-674), compositeCCM [9]
+ * (:630-645), toneCurveLut [4096][3] (buildToneCurveLut, :382-416). Any pointer may be NULL. */
+int derp_isp_tables(const derp_isp* isp, float* vignette_h, float* vignette_v, float* ccm9, float* tone_lut);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* computeCost evaluations and (evaluation, src) pairs reaching computeSSD since the last reset:
  * the N_cost / N_pair of BASELINE.md's B_alg = 64*N_cost + 272*N_pair. */
