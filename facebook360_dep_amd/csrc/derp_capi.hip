@@ -3569,3 +3569,4 @@ int derp_render_format(derp_ctx* c, const char* format, const derp_render_params
 
 #include "derp_sequence.h"
 #include "derp_isp.h"
+#include "derp_sim.h"

@@ -125,6 +125,11 @@ EXPORTS = [
     "derp_seq_run", "derp_seq_stats", "derp_seq_stats_reset", "derp_seq_exchange_exposed_ms",
     "derp_isp_config_default", "derp_isp_create", "derp_isp_destroy", "derp_isp_output_size", "derp_isp_process",
     "derp_isp_stage", "derp_isp_tables",
+    "derp_sim_scene_create", "derp_sim_scene_destroy", "derp_sim_scene_icosahedrons", "derp_sim_scene_cubes",
+    "derp_sim_scene_ground_plane", "derp_sim_scene_add_triangle", "derp_sim_bvh_build", "derp_sim_scene_counts",
+    "derp_sim_scene_get", "derp_sim_perlin_table", "derp_sim_icosahedron", "derp_sim_noise", "derp_sim_trace_host", "derp_sim_create",
+    "derp_sim_destroy", "derp_sim_upload", "derp_sim_render_camera", "derp_sim_render_equirect", "derp_sim_trace_rays",
+    "derp_sim_stage_size", "derp_sim_stage",
 ]
 
 _lib = None
@@ -150,6 +155,9 @@ def lib():
         _lib.derp_last_error.argtypes = [C.c_void_p]
         _lib.derp_host_minstd_uniform.restype = C.c_float
         _lib.derp_host_minstd_uniform.argtypes = [C.c_int, C.c_uint64, C.c_float, C.c_float]
+        _lib.derp_sim_scene_create.restype = C.c_void_p
+        _lib.derp_sim_scene_destroy.argtypes = [C.c_void_p]
+        _lib.derp_sim_scene_destroy.restype = None
     return _lib
 
 
@@ -924,3 +932,159 @@ class Isp:
         ccm, lut = np.zeros((3, 3), np.float32), np.zeros((4096, 3), np.float32)
         self._ck(lib().derp_isp_tables(self.h, _p(vh), _p(vv), _p(ccm), _p(lut)))
         return vh, vv, ccm, lut
+
+
+# ---------------------------------------------------------------- RigSimulator (derp_sim_*)
+SIM_TRIANGLE = np.dtype([("v0", "<f4", 3), ("v1", "<f4", 3), ("v2", "<f4", 3), ("e1", "<f4", 3), ("e2", "<f4", 3),
+                         ("normal", "<f4", 3), ("color", "<f4", 3)])  # derp_sim_triangle
+SIM_NODE = np.dtype([("center", "<f4", 3), ("radius", "<f4"), ("skip", "<i4"), ("first", "<i4"), ("count", "<i4"),
+                     ("n_children", "<i4")])  # derp_sim_node
+SIM_STAGES = {"origin": (0, np.float32, 3), "direction": (1, np.float32, 3), "hit": (2, np.int32, 1),
+              "distance": (3, np.float32, 1), "color": (4, np.float32, 3)}
+
+
+class SimParams(C.Structure):
+    """derp_sim_params (include/derp_hip.h)."""
+    _fields_ = [("ceiling_position", C.c_double), ("ceiling_width", C.c_double), ("ceiling_depth", C.c_double),
+                ("marble_scale", C.c_double), ("marble", C.c_int32), ("pad", C.c_int32)]
+
+
+class SimScene:
+    """RigSimulator's triangles and sphere tree, built on the host (no device): the builders append, build_bvh()
+    flattens. The random builders draw from the C library's rand(): srand() first for a repeatable scene."""
+
+    def __init__(self):
+        self.h = C.c_void_p(lib().derp_sim_scene_create())
+
+    def close(self):
+        if self.h:
+            lib().derp_sim_scene_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def _ck(rc):
+        if rc:
+            raise DerpError("derp_sim_scene: bad arguments")
+
+    def icosahedrons(self, count=250, min_dist=100.0, max_dist=250.0, min_radius=20.0, max_radius=50.0, red_triangle=False):
+        self._ck(lib().derp_sim_scene_icosahedrons(self.h, int(count), C.c_double(min_dist), C.c_double(max_dist),
+                                                   C.c_double(min_radius), C.c_double(max_radius), int(bool(red_triangle))))
+        return self
+
+    def cubes(self):
+        self._ck(lib().derp_sim_scene_cubes(self.h))
+        return self
+
+    def ground_plane(self, dist=1.70):
+        self._ck(lib().derp_sim_scene_ground_plane(self.h, C.c_double(dist)))
+        return self
+
+    def add_triangle(self, v0, v1, v2, color_bgr):
+        a = [np.ascontiguousarray(v, dtype=np.float32) for v in (v0, v1, v2, color_bgr)]
+        self._ck(lib().derp_sim_scene_add_triangle(self.h, *[_p(v) for v in a]))
+        return self
+
+    def build_bvh(self, leaf_threshold=20, split_k=5, max_depth=50):
+        self._ck(lib().derp_sim_bvh_build(self.h, leaf_threshold, split_k, max_depth))
+        return self
+
+    def arrays(self):
+        """(triangles [SIM_TRIANGLE], nodes [SIM_NODE], leaf indices int32)."""
+        nt, nn, nl = C.c_int(), C.c_int(), C.c_int()
+        self._ck(lib().derp_sim_scene_counts(self.h, C.byref(nt), C.byref(nn), C.byref(nl)))
+        tris, nodes, leaf = np.zeros(nt.value, SIM_TRIANGLE), np.zeros(nn.value, SIM_NODE), np.zeros(nl.value, np.int32)
+        self._ck(lib().derp_sim_scene_get(self.h, _p(tris), _p(nodes), _p(leaf)))
+        return tris, nodes, leaf
+
+    def trace_host(self, rays):
+        """Single-thread CPU tracer (geometry only): rays [n, 6] -> [n, 4] (b, g, r, depth)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((rays.shape[0], 4), np.float32)
+        self._ck(lib().derp_sim_trace_host(self.h, _p(rays), C.c_size_t(rays.shape[0]), _p(out)))
+        return out
+
+
+def sim_noise(bgr, amplitude):
+    """corruptImageWithNoise in place on a float32 [h, w, 3] image (rand() of the C library)."""
+    assert bgr.dtype == np.float32 and bgr.flags.c_contiguous and bgr.ndim == 3 and bgr.shape[2] == 3
+    if lib().derp_sim_noise(_p(bgr), bgr.shape[1], bgr.shape[0], C.c_double(amplitude)):
+        raise DerpError("derp_sim_noise: bad arguments")
+    return bgr
+
+
+def sim_perlin_table():
+    p = np.zeros(512, np.uint8)
+    lib().derp_sim_perlin_table(_p(p))
+    return p
+
+
+class Sim:
+    """RigSimulator's tracer on the GPU (derp_sim_create .. derp_sim_destroy)."""
+
+    def __init__(self, device=0):
+        h = C.c_void_p()
+        if lib().derp_sim_create(C.byref(h), device):
+            raise DerpError(lib().derp_last_error(None).decode())
+        self.h = h
+
+    def _ck(self, rc):
+        if rc:
+            raise DerpError(lib().derp_last_error(None).decode())
+
+    def close(self):
+        if self.h:
+            lib().derp_sim_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def upload(self, triangles, nodes, leaf, skybox, ceiling=None, ceiling_position=0.0, ceiling_width=0.0,
+               ceiling_depth=0.0, marble=False, marble_scale=0.1):
+        """triangles / nodes / leaf as SimScene.arrays() gives them; skybox and ceiling uint8 BGR [h, w, 3]."""
+        triangles = np.ascontiguousarray(triangles, dtype=SIM_TRIANGLE)
+        nodes = np.ascontiguousarray(nodes, dtype=SIM_NODE)
+        leaf = np.ascontiguousarray(leaf, dtype=np.int32)
+        skybox = np.ascontiguousarray(skybox, dtype=np.uint8)
+        assert skybox.ndim == 3 and skybox.shape[2] == 3
+        cw = ch = 0
+        if ceiling is not None:
+            ceiling = np.ascontiguousarray(ceiling, dtype=np.uint8)
+            assert ceiling.ndim == 3 and ceiling.shape[2] == 3
+            ch, cw = ceiling.shape[:2]
+        p = SimParams(ceiling_position, ceiling_width, ceiling_depth, marble_scale, int(bool(marble)), 0)
+        self._ck(lib().derp_sim_upload(self.h, _p(triangles), len(triangles), _p(nodes), len(nodes), _p(leaf), len(leaf),
+                                       _p(skybox), skybox.shape[1], skybox.shape[0],
+                                       _p(ceiling) if ceiling is not None else None, cw, ch, C.byref(p)))
+
+    def render_camera(self, cam, aas=1):
+        """cam: a rig-file camera dict or CameraDesc -> (bgr float32 [h, w, 3] in 0..255, depth float32 [h, w])."""
+        d = cam if isinstance(cam, CameraDesc) else camera_desc(cam)
+        w, h = int(d.resolution[0]), int(d.resolution[1])
+        bgr, depth = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32)
+        self._ck(lib().derp_sim_render_camera(self.h, C.byref(d), int(aas), _p(bgr), _p(depth)))
+        return bgr, depth
+
+    def render_equirect(self, w, h, aas=1, stereo=False, interpupillary_radius=3.2):
+        """mono: (bgr, inverse depth); stereo: (left, right)."""
+        a = np.zeros((h, w, 3), np.float32)
+        b = np.zeros((h, w, 3), np.float32) if stereo else np.zeros((h, w), np.float32)
+        self._ck(lib().derp_sim_render_equirect(self.h, w, h, int(aas), int(bool(stereo)), C.c_double(interpupillary_radius),
+                                                _p(a), _p(b) if stereo else None, None if stereo else _p(b)))
+        return a, b
+
+    def trace_rays(self, rays):
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        self._ck(lib().derp_sim_trace_rays(self.h, _p(rays), C.c_size_t(rays.shape[0])))
+
+    def stage(self, name, eye=0):
+        """A supersampled plane of the last render: origin, direction, hit, distance, color."""
+        idx, dtype, cn = SIM_STAGES[name]
+        w, h = C.c_int(), C.c_int()
+        self._ck(lib().derp_sim_stage_size(self.h, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value, cn) if cn > 1 else (h.value, w.value), dtype)
+        self._ck(lib().derp_sim_stage(self.h, idx, int(eye), _p(out)))
+        return out

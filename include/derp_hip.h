@@ -565,6 +565,87 @@ int derp_isp_stage(derp_isp* isp, int stage, float* out);
  * (:630-645), toneCurveLut [4096][3] (buildToneCurveLut, :382-416). Any pointer may be NULL. */
 int derp_isp_tables(const derp_isp* isp, float* vignette_h, float* vignette_v, float* ccm9, float* tone_lut);
 
+/* ---- RigSimulator: a ray-traced procedural scene as a rig sees it (source/rig/RigSimulator.cpp) -------------
+ * The scene and its sphere tree are built on the host (derp_sim_scene_*: no device, no context), flattened in
+ * pre-order and handed to a derp_sim, which traces one ray per supersampled pixel on the GPU. */
+typedef struct {        /* render::Triangle, RaytracingPrimitives.h:35-50 */
+  float v0[3], v1[3], v2[3];
+  float e1[3], e2[3];   /* v1 - v0, v2 - v0 */
+  float normal[3];      /* e1 x e2, normalised */
+  float color[3];       /* BGR in 0..1 */
+} derp_sim_triangle;
+typedef struct {        /* one BoundingVolumeHierarchy node of the pre-order flat tree */
+  float center[3];
+  float radius;
+  int32_t skip;         /* index of the first node behind this node's subtree (the walk goes there on a sphere miss) */
+  int32_t first;        /* leaf: offset of its triangles in the leaf index list */
+  int32_t count;        /* leaf: number of triangles (may be 0); inner node: -1 */
+  int32_t n_children;   /* inner node: number of children (they follow in order); leaf: 0 */
+} derp_sim_node;
+typedef struct derp_sim_scene derp_sim_scene;
+derp_sim_scene* derp_sim_scene_create(void);
+void derp_sim_scene_destroy(derp_sim_scene* scene);
+/* The builders append to the scene; the random ones call the C library's rand() in the reference's order.
+ * makeIcosahedronScene (RigSimulator.cpp:264-289, flags num_random_icosahedrons, min / max_icosahedron_dist,
+ * min / max_icosahedron_radius, red_triangle), makeCubesScene (:291-343), makeGroundPlaneScene (:345-358). */
+int derp_sim_scene_icosahedrons(derp_sim_scene* scene, int count, double min_dist, double max_dist, double min_radius,
+                                double max_radius, int red_triangle);
+int derp_sim_scene_cubes(derp_sim_scene* scene);
+int derp_sim_scene_ground_plane(derp_sim_scene* scene, double ground_plane_dist_m);
+/* Triangle::Triangle of three vertices and a BGR colour */
+int derp_sim_scene_add_triangle(derp_sim_scene* scene, const float* v0, const float* v1, const float* v2,
+                                const float* color_bgr);
+/* BoundingVolumeHierarchy::makeBVH (BoundingVolumeHierarchy.h:32-114); the reference passes 20, 5, 50 */
+int derp_sim_bvh_build(derp_sim_scene* scene, int leaf_threshold, int split_k, int max_depth);
+int derp_sim_scene_counts(const derp_sim_scene* scene, int* n_triangles, int* n_nodes, int* n_leaf_indices);
+/* triangles [n_triangles], nodes [n_nodes], leaf index list [n_leaf_indices]; any pointer may be NULL */
+int derp_sim_scene_get(const derp_sim_scene* scene, derp_sim_triangle* triangles, derp_sim_node* nodes,
+                       int32_t* leaf_indices);
+/* Ken Perlin's reference permutation ("Improved Noise", 2002) twice over: the p[512] of PerlinNoise.h */
+void derp_sim_perlin_table(uint8_t* p512);
+/* the unit icosahedron of the scenes and of the dodecahedron / icosahedron rigs (icosahedron_data, :123-143): 12
+ * vertices x 3, 20 faces x 3 vertex indices */
+void derp_sim_icosahedron(float* vertices36, int32_t* faces60);
+/* corruptImageWithNoise (:494-508) on a [h][w][3] float image in 0..255, rand() in row order */
+int derp_sim_noise(float* bgr, int w, int h, double amplitude);
+/* traceRayToGetColor on the host, one thread: the CPU baseline of tools/sim_timing.py. rays = n x (origin, dir);
+ * out_bgrd = n x (b, g, r, depth). The sky lookup is not part of it (a miss gives 0, 0, 0, FLT_MAX). */
+int derp_sim_trace_host(const derp_sim_scene* scene, const float* rays6, size_t n, float* out_bgrd);
+
+typedef struct {
+  double ceiling_position, ceiling_width, ceiling_depth; /* --ceiling_*: used when a ceiling image is uploaded */
+  double marble_scale;                                    /* --marble_scale 0.1 */
+  int32_t marble;                                         /* --marble */
+  int32_t pad;
+} derp_sim_params;
+enum {
+  DERP_SIM_STAGE_ORIGIN = 0, /* [H][W][3] f32 */
+  DERP_SIM_STAGE_DIRECTION,  /* [H][W][3] f32 */
+  DERP_SIM_STAGE_HIT,        /* [H][W] i32: triangle index, -1 sky, -2 ceiling, -3 outside the image circle */
+  DERP_SIM_STAGE_DISTANCE,   /* [H][W] f32: the depth the ray returns (FLT_MAX for sky / outside) */
+  DERP_SIM_STAGE_COLOR       /* [H][W][3] f32 BGR x 255, before the downscale */
+};
+typedef struct derp_sim derp_sim;
+/* Fails without a HIP device: the tracer has no CPU path behind this object. */
+int derp_sim_create(derp_sim** out, int device);
+void derp_sim_destroy(derp_sim* sim);
+/* skybox / ceiling: 8-bit BGR as IMREAD_COLOR gives them; ceiling_bgr NULL = no ceiling (--ceiling_path empty) */
+int derp_sim_upload(derp_sim* sim, const derp_sim_triangle* triangles, int n_triangles, const derp_sim_node* nodes,
+                    int n_nodes, const int32_t* leaf_indices, int n_leaf_indices, const uint8_t* skybox_bgr, int sky_w,
+                    int sky_h, const uint8_t* ceiling_bgr, int ceiling_w, int ceiling_h, const derp_sim_params* params);
+/* renderCamera (:591-625) without the noise: bgr_out [h][w][3] f32 in 0..255, depth_out [h][w] f32, (w, h) the
+ * camera's resolution, after the aas x aas INTER_AREA downscale */
+int derp_sim_render_camera(derp_sim* sim, const derp_camera_desc* cam, int aas, float* bgr_out, float* depth_out);
+/* renderMonoEquirect (:520-547; bgr_a = colour, aux_out = inverse depth clamped to 0..1, bgr_b unused) or
+ * renderStereoEquirect (:549-589; bgr_a = left, bgr_b = right, aux_out unused) */
+int derp_sim_render_equirect(derp_sim* sim, int w, int h, int aas, int stereo, double interpupillary_radius,
+                             float* bgr_a, float* bgr_b, float* aux_out);
+/* re-trace caller-given rays (n x (origin, dir)) as one row of n pixels; read the result with derp_sim_stage */
+int derp_sim_trace_rays(derp_sim* sim, const float* rays6, size_t n);
+/* a plane of the last render at its supersampled size (`eye` 1 = the right eye of a stereo equirect); tests */
+int derp_sim_stage_size(const derp_sim* sim, int* width, int* height);
+int derp_sim_stage(derp_sim* sim, int stage, int eye, void* out);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 /* computeCost evaluations and (evaluation, src) pairs reaching computeSSD since the last reset:
  * the N_cost / N_pair of BASELINE.md's B_alg = 64*N_cost + 272*N_pair. */
