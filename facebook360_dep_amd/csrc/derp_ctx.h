@@ -1,0 +1,184 @@
+// The depth context behind the C-ABI (include/derp_hip.h): the rig, the HBM-resident pyramid of every frame slot, the
+// working level of the level loop, profiling and developer switches, and one lazily created state per tool family (each
+// defined in that family's derp_*_api.h). Included by derp_capi.hip (one translation unit) after the kernel headers.
+#pragma once
+
+namespace {
+
+enum Stage {
+  ST_FOV = 0,
+  ST_VARIANCE,
+  ST_OWN_BIAS,
+  ST_UPSAMPLE,
+  ST_PROJ_WARP,
+  ST_REPROJECT,
+  ST_PROJ_BIAS,
+  ST_BRUTE,
+  ST_RANDOM,
+  ST_PINGPONG,
+  ST_MISMATCH,
+  ST_BILATERAL,
+  ST_MEDIAN,
+  ST_MASKFOV,
+  ST_TEMPORAL,
+  ST_LANES,  // wall of a level whose frames ran on overlapping work lanes (their per-stage spans overlap in time)
+  ST_COUNT
+};
+const char* kStageNames[ST_COUNT] = {"fov_mask",  "variance",    "own_bias",         "upsample",  "proj_warp",
+                                     "reproject", "proj_bias",   "brute_force",      "random_proposals",
+                                     "ping_pong", "mismatches",  "bilateral",        "median",    "mask_fov",
+                                     "temporal",  "lanes_wall"};
+constexpr int kMaxLevels = 24;
+
+struct TimedSpan {
+  int stage, level;
+  hipEvent_t a, b;
+};
+
+struct LanczosTab {
+  DevBuf ofs, coef;
+};
+
+struct AreaTabDev {  // computeResizeAreaTab of one axis, resident in HBM
+  DevBuf start, si, alpha;
+  int iscale = 0;
+};
+
+// Everything processLevel writes per frame. The context has one and every work lane has one; the rig-only tables of a
+// level (projWarp, projWarpInv, rayDir, behind, resampling tables) are shared by the lanes and stay on the context.
+struct WorkSet {
+  DevBuf srcVar, ownBias, fovMask, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
+  DevBuf tileSeen;    // k_reproject_bias: per (table, tile) whether any map position is valid
+  DevBuf projColor, projBias;
+  DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)
+  DevBuf bruteCost, bruteConf, lanczosTmp, staging, stagingB;
+  int colorTablesCleanLevel = -1;  // level whose colour / bias tables were written in full since its warps were built
+};
+
+// HBM-resident pyramid of one frame, per level: colour, fg masks, background disparity, result
+struct FramePyramid {
+  std::vector<DevBuf> color, fg, bg, disp;
+  std::vector<char> haveBg, haveDisp;
+};
+
+struct WorkLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  WorkSet w;
+};
+
+// per tool family, defined in its derp_*_api.h and created by the family's first call that needs it
+struct SmrState; struct RephotoState; struct PointsState; struct MeshState;
+
+}  // namespace
+
+struct derp_ctx {
+  derp_ctx();  // both defined at the end of derp_capi.hip, where the family states are complete types
+  ~derp_ctx();
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipStream_t copyStream = nullptr;  // input uploads of a frame that is not being computed (sequence driver), with
+  DevBuf copyStaging;                // their own staging buffer: they overlap the compute of the frame before
+  std::string err;
+  std::string* errSink() {
+    return &err;
+  }
+  derp_options opt;
+  // ---- the rig
+  int S = 0, D = 0;
+  std::vector<Cam> camsSrcH, camsDstH;
+  std::vector<int> dst2srcH;
+  std::vector<derp_camera_desc> descDstH;  // the destinations as the rig file holds them (un-normalised: derp_points_* etc.)
+  DevBuf camsSrc, camsDst, dst2src;
+
+  // ---- the pyramid and its frame slots
+  int numLevels = 0, widthFull = 0, heightFull = 0;
+  std::vector<int> LW, LH;
+  // one pyramid per frame slot (derp_set_frame_slots / derp_select_frame: several frames of one sequence resident on
+  // this GPU); the level loop works on the selected one
+  std::vector<FramePyramid> frames;
+  int curSlot = 0;
+  FramePyramid& frame() {
+    return frames[curSlot];
+  }
+  DevBuf fullFrame;  // the pyramid builder's full-size input
+  DevBuf devMask;    // derp_dev_mask result (not a working buffer)
+
+  // ---- the working level
+  int cur = -1;
+  int DB = 0;  // dst batch that fits the table budget
+  WorkSet w;             // the per-frame working set in use: the context's own, or a lane's while its frame runs
+  DevBuf temporalCarry;  // accumulators of a temporal window longer than one launch holds
+  DevBuf projWarp, projWarpInv;
+  DevBuf rayDir, behind;  // per destination pixel: ray direction [3][D][n] f64, sources facing away [D][n] (k_pixel_rays)
+  int warpCachedLevel = -1;
+  bool randomRanThisLevel = false;  // cost / confidence hold random-proposal results for this level
+  bool tablesValid = false;
+  std::map<std::pair<int, int>, LanczosTab> lanczos;  // (map nodes keep their addresses: get_lanczos / get_area_tab
+  std::map<std::pair<int, int>, AreaTabDev> areaTabs;  // hand out pointers into them)
+  DevBuf spiral;
+  int spiralN = 0, spiralRadius = -1;
+  // Work lanes (round 6): a second, third ... working set + stream for processLevel of ANOTHER frame of a sequence at the
+  // same coarse level (derp_seq_level_compute). The frames of a level are independent, and at the coarse levels one
+  // frame's kernels fill a fraction of the chip (level 6 of the 16-camera rig: 784 waves for 4096 wave slots) and are
+  // bound by their own serial latency — on lanes the frames' kernels overlap. A lane holds everything processLevel writes
+  // per frame (a WorkSet); the rig-only tables of the level (projWarp, projWarpInv, rayDir, behind, resampling tables) stay
+  // shared.
+  std::vector<std::unique_ptr<WorkLane>> lanes;
+  hipEvent_t laneReady = nullptr;  // recorded on the main stream behind what the lanes' frames depend on
+  int activeLane = -1;             // the lane whose work set is swapped in (-1: the context's own)
+
+  // ---- profiling and developer switches
+  DevBuf counters;  // [ST_COUNT][kMaxLevels][4] u64
+  bool profiling = false;
+  std::vector<TimedSpan> spans;
+  double accMs[ST_COUNT][kMaxLevels] = {};
+  int accLaunch[ST_COUNT][kMaxLevels] = {};
+  int xcdRotate = 1;
+  bool noMemo = false;  // DERP_NO_MEMO (developer switch), read once in derp_create
+  // ping-pong's candidate loop: compacted into full waves of (pixel, candidate) tasks, or one pixel per lane
+  // (DERP_PP_COMPACT=0, developer A/B switch; same results), read once in derp_create
+  bool ppCompact = true;
+  // waves per SIMD of the random-proposal / ping-pong kernels (0 = what their registers and LDS allow: four up to 16
+  // cameras): a launch can ask for fewer by reserving more LDS per (one-wave) block — DERP_RANDOM_WAVES / DERP_PP_WAVES,
+  // developer A/B switches
+  int randomWaves = 0, ppWaves = 0;
+  size_t ldsPerCu = 160 * 1024;  // hipDeviceProp.maxSharedMemoryPerMultiProcessor (derp_create)
+  bool noTemporalTile = false;  // DERP_NO_TEMPORAL_TILE (developer A/B: the direct form of the temporal filter)
+  bool noBlankSkip = false;     // DERP_NO_BLANK_SKIP (developer A/B: every frame rewrites the blank tiles of the colour tables)
+  // ---- the tool families' states
+  std::unique_ptr<SmrState> smr;
+  std::unique_ptr<RephotoState> rephoto;
+  std::unique_ptr<PointsState> points;
+  std::unique_ptr<MeshState> mesh;
+};
+
+namespace {
+
+// the context's error channel (derp_last_error(c)); a null context drops the text
+int fail(derp_ctx* c, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vfail(c ? &c->err : nullptr, fmt, ap);
+  va_end(ap);
+  return 1;
+}
+
+// the prologue of the entry points that take nothing to validate but the context: bind its device to the thread
+int use_device(derp_ctx* c) {
+  if (!c) {
+    return 1;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return 0;
+}
+
+// `cam` indexes a destination camera of the context
+int check_camera(derp_ctx* c, int cam) {
+  if (cam < 0 || cam >= c->D) {
+    return fail(c, "bad camera index %d (the context has %d)", cam, c->D);
+  }
+  return 0;
+}
+
+}  // namespace

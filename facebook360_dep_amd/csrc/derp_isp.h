@@ -594,21 +594,12 @@ struct derp_isp {
   hipStream_t stream = nullptr;
   DevBuf in, raw0, raw1, raw2, dem, col, lp, shp, scr, gV, gH, bit, dVigH, dVigV, dLut, stale, out;
   std::vector<float> hostPlane;
+  std::string* errSink() const {  // every derp_isp_* call reports through derp_last_error(nullptr)
+    return &g_create_error;
+  }
 };
 
 namespace {
-
-int isp_fail(const std::string& m) {
-  g_create_error = m;
-  return 1;
-}
-#define ISPCHK(expr)                                                                            \
-  do {                                                                                          \
-    const hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) {                                                                     \
-      return isp_fail(std::string(#expr " failed: ") + hipGetErrorString(e_));                  \
-    }                                                                                           \
-  } while (0)
 
 // setup() :573-618; false for a pattern it does not know
 bool isp_pattern(const char* bayer, unsigned* pat) {
@@ -659,30 +650,30 @@ int derp_isp_create(derp_isp** out, int device, const derp_isp_config* cfg, int 
   }
   *out = nullptr;
   if (!cfg) {
-    return isp_fail("derp_isp_create: no config");
+    return create_fail("derp_isp_create: no config");
   }
   // ---- refusals, before anything is allocated
   if (demosaic_filter < 0 || demosaic_filter > DERP_ISP_CHROMA_SUPPRESSED) {  // setDemosaicFilter :949-953
-    return isp_fail("expecting Demosaic filter in [0,3]");
+    return create_fail("expecting Demosaic filter in [0,3]");
   }
   if (demosaic_filter == DERP_ISP_FREQUENCY) {
-    return isp_fail("frequency demosaic is not built (it needs a DCT of the whole plane)");
+    return create_fail("frequency demosaic is not built (it needs a DCT of the whole plane)");
   }
   if (pow2_downscale != 1 && pow2_downscale != 2 && pow2_downscale != 4 && pow2_downscale != 8) {  // setResize :955-959
-    return isp_fail("expecting a resize value of 1, 2, 4, or 8. got " + std::to_string(pow2_downscale));
+    return create_fail("expecting a resize value of 1, 2, 4, or 8. got " + std::to_string(pow2_downscale));
   }
   if (cfg->width <= 0 || cfg->height <= 0 || cfg->width % 2 || cfg->height % 2) {  // loadImageFromSensor :769-772
-    return isp_fail("sensor width and height must be even and non-zero");
+    return create_fail("sensor width and height must be even and non-zero");
   }
   if (cfg->bits_per_pixel != 8 && cfg->bits_per_pixel != 16) {  // RawUtil.cpp:111
-    return isp_fail("Unsupported precision: bitsPerPixel must be 8 or 16");
+    return create_fail("Unsupported precision: bitsPerPixel must be 8 or 16");
   }
   if ((size_t)cfg->width * cfg->height > ((size_t)1 << 28)) {
-    return isp_fail("sensor larger than 2^28 pixels");
+    return create_fail("sensor larger than 2^28 pixels");
   }
   unsigned pat = 0;
   if (strlen(cfg->bayer_pattern) != 4 || !isp_pattern(cfg->bayer_pattern, &pat)) {
-    return isp_fail("bayerPattern must be RGGB, GRBG, GBRG or BGGR");
+    return create_fail("bayerPattern must be RGGB, GRBG, GBRG or BGGR");
   }
   int planeOf[4] = {0, 1, 2, 3};
   const bool planar = cfg->plane_order[0] != 0;
@@ -704,36 +695,23 @@ int derp_isp_create(derp_isp** out, int device, const derp_isp_config* cfg, int 
       }
     }
     if (seen != 15) {
-      return isp_fail("planeOrder must hold the four letters of bayerPattern");
+      return create_fail("planeOrder must hold the four letters of bayerPattern");
     }
   }
   if (cfg->n_rolloff_h < 1 || cfg->n_rolloff_h > DERP_ISP_MAX_ROLLOFF || cfg->n_rolloff_v < 1 ||
       cfg->n_rolloff_v > DERP_ISP_MAX_ROLLOFF) {
-    return isp_fail("vignetteRollOffH / vignetteRollOffV must hold 1.." + std::to_string((int)DERP_ISP_MAX_ROLLOFF) + " points");
+    return create_fail("vignetteRollOffH / vignetteRollOffV must hold 1.." + std::to_string((int)DERP_ISP_MAX_ROLLOFF) + " points");
   }
   if (cfg->stuck_pixel_threshold < 0 || cfg->stuck_pixel_radius < 0) {
-    return isp_fail("Check failed: stuckPixelThreshold >= 0");
+    return create_fail("Check failed: stuckPixelThreshold >= 0");
   }
   const int w = cfg->width / pow2_downscale, h = cfg->height / pow2_downscale;  // setDimensions :1239-1245
   const int least = demosaic_filter == DERP_ISP_EDGE_AWARE ? 5 : 3;  // one reflection must stay inside the plane
   if (w < least || h < least || cfg->stuck_pixel_radius >= std::min(w, h)) {
-    return isp_fail("output of " + std::to_string(w) + " x " + std::to_string(h) + " is too small for this filter");
-  }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-    return isp_fail("no HIP device present: the ISP has no CPU fallback");
-  }
-  if (device < 0 || device >= count) {
-    return isp_fail("HIP device index out of range");
+    return create_fail("output of " + std::to_string(w) + " x " + std::to_string(h) + " is too small for this filter");
   }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-    return isp_fail("hipGetDeviceProperties failed");
-  }
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !getenv("DERP_ALLOW_ANY_ARCH")) {
-    return isp_fail(std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-  }
-  ISPCHK(hipSetDevice(device));
+  TRY(open_device(device, "the ISP", &prop));
   std::unique_ptr<derp_isp> owner(new derp_isp);
   derp_isp* s = owner.get();
   s->device = device;
@@ -786,12 +764,12 @@ int derp_isp_create(derp_isp** out, int device, const derp_isp_config* cfg, int 
       (ea && (s->gV.ensure(plane) || s->gH.ensure(plane) || s->bit.ensure(n))) || s->dVigH.ensure(s->vigH.size() * 4) ||
       s->dVigV.ensure(s->vigV.size() * 4) || s->dLut.ensure(s->lut.size() * 4) || s->stale.ensure(3 * sizeof(float)) ||
       s->out.ensure(3 * n * (cfg->bits_per_pixel / 8))) {
-    return isp_fail("out of device memory");
+    return create_fail("out of device memory");
   }
-  ISPCHK(hipMemcpy(s->dVigH.p, s->vigH.data(), s->vigH.size() * 4, hipMemcpyHostToDevice));
-  ISPCHK(hipMemcpy(s->dVigV.p, s->vigV.data(), s->vigV.size() * 4, hipMemcpyHostToDevice));
-  ISPCHK(hipMemcpy(s->dLut.p, s->lut.data(), s->lut.size() * 4, hipMemcpyHostToDevice));
-  ISPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+  HIPCHK(s, hipMemcpy(s->dVigH.p, s->vigH.data(), s->vigH.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(s, hipMemcpy(s->dVigV.p, s->vigV.data(), s->vigV.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(s, hipMemcpy(s->dLut.p, s->lut.data(), s->lut.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(s, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   *out = owner.release();
   return 0;
 }
@@ -808,7 +786,7 @@ void derp_isp_destroy(derp_isp* s) {
 
 int derp_isp_output_size(const derp_isp* s, int* width, int* height) {
   if (!s || !width || !height) {
-    return isp_fail("derp_isp_output_size: bad arguments");
+    return create_fail("derp_isp_output_size: bad arguments");
   }
   *width = s->w;
   *height = s->h;
@@ -817,22 +795,22 @@ int derp_isp_output_size(const derp_isp* s, int* width, int* height) {
 
 int derp_isp_process(derp_isp* s, const void* raw, size_t raw_bytes, void* out_bgr) {
   if (!s || !raw || !out_bgr) {
-    return isp_fail("derp_isp_process: bad arguments");
+    return create_fail("derp_isp_process: bad arguments");
   }
   const derp_isp_config& k = s->cfg;
   const int bytes = k.bits_per_pixel / 8, w = s->w, h = s->h;
   const size_t inBytes = (size_t)k.width * k.height * bytes, n = (size_t)w * h;
   if (raw_bytes < inBytes) {  // readRawImage, RawUtil.cpp:37
-    return isp_fail("unexpected end of file: raw image holds " + std::to_string(raw_bytes) + " bytes, the sensor " +
+    return create_fail("unexpected end of file: raw image holds " + std::to_string(raw_bytes) + " bytes, the sensor " +
                     std::to_string(inBytes));
   }
-  ISPCHK(hipSetDevice(s->device));
+  HIPCHK(s, hipSetDevice(s->device));
   hipStream_t st = s->stream;
   s->processed = false;
-  ISPCHK(hipMemcpyAsync(s->in.p, raw, inBytes, hipMemcpyHostToDevice, st));
+  HIPCHK(s, hipMemcpyAsync(s->in.p, raw, inBytes, hipMemcpyHostToDevice, st));
   const dim3 b2(32, 8), g2((w + 31) / 32, (h + 7) / 8);
   const dim3 b16(16, 16), g16((w + 15) / 16, (h + 15) / 16);
-  const unsigned g1 = (unsigned)((n + 255) / 256);
+  const unsigned g1 = blocks_of(n, 256);
   if (bytes == 1) {
     k_isp_load<uint8_t><<<g2, b2, 0, st>>>(s->in.as<uint8_t>(), s->raw0.as<float>(), s->load);
   } else {
@@ -843,10 +821,10 @@ int derp_isp_process(derp_isp* s, const void* raw, size_t raw_bytes, void* out_b
   const float* mosaic = s->raw1.as<float>();
   if (k.stuck_pixel_radius > 0) {  // host, between two device phases
     s->hostPlane.resize(n);
-    ISPCHK(hipMemcpyAsync(s->hostPlane.data(), s->raw1.p, n * 4, hipMemcpyDeviceToHost, st));
-    ISPCHK(hipStreamSynchronize(st));
+    HIPCHK(s, hipMemcpyAsync(s->hostPlane.data(), s->raw1.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(s, hipStreamSynchronize(st));
     isp_remove_stuck_pixels(s->hostPlane.data(), w, h, s->pat, k);
-    ISPCHK(hipMemcpyAsync(s->raw2.p, s->hostPlane.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(s, hipMemcpyAsync(s->raw2.p, s->hostPlane.data(), n * 4, hipMemcpyHostToDevice, st));
     mosaic = s->raw2.as<float>();
   }
   const IspMosaic M{mosaic, w, h, s->pat};
@@ -867,7 +845,7 @@ int derp_isp_process(derp_isp* s, const void* raw, size_t raw_bytes, void* out_b
   k_isp_color<<<g1, 256, 0, st>>>(s->dem.as<float>(), s->col.as<float>(), s->dLut.as<float>(), n, s->ccm);
   const float* last = s->col.as<float>();
   if (s->sharpen) {
-    ISPCHK(hipMemsetAsync(s->stale.p, 0, 3 * sizeof(float), st));
+    HIPCHK(s, hipMemsetAsync(s->stale.p, 0, 3 * sizeof(float), st));
     k_isp_iir_rows<<<dim3((h + 63) / 64, 3), 64, 0, st>>>(s->col.as<float>(), s->scr.as<float>(), s->lp.as<float>(),
                                                           s->stale.as<float>(), w, h, s->alpha);
     k_isp_iir_cols<<<dim3((w + 63) / 64, 3), 64, 0, st>>>(s->lp.as<float>(), s->scr.as<float>(), s->stale.as<float>(), w, h,
@@ -880,19 +858,19 @@ int derp_isp_process(derp_isp* s, const void* raw, size_t raw_bytes, void* out_b
   } else {
     k_isp_output<uint16_t><<<g1, 256, 0, st>>>(last, s->out.as<uint16_t>(), n, 65535.0f);
   }
-  ISPCHK(hipGetLastError());
-  ISPCHK(hipMemcpyAsync(out_bgr, s->out.p, 3 * n * bytes, hipMemcpyDeviceToHost, st));
-  ISPCHK(hipStreamSynchronize(st));
+  KCHECK(s);
+  HIPCHK(s, hipMemcpyAsync(out_bgr, s->out.p, 3 * n * bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(s, hipStreamSynchronize(st));
   s->processed = true;
   return 0;
 }
 
 int derp_isp_stage(derp_isp* s, int stage, float* out) {
   if (!s || !out) {
-    return isp_fail("derp_isp_stage: bad arguments");
+    return create_fail("derp_isp_stage: bad arguments");
   }
   if (!s->processed) {
-    return isp_fail("derp_isp_stage: no image was processed yet");
+    return create_fail("derp_isp_stage: no image was processed yet");
   }
   const size_t plane = (size_t)s->w * s->h * sizeof(float);
   const void* src = nullptr;
@@ -906,21 +884,21 @@ int derp_isp_stage(derp_isp* s, int stage, float* out) {
     case DERP_ISP_STAGE_LOWPASS:
     case DERP_ISP_STAGE_SHARPENED:
       if (!s->sharpen) {
-        return isp_fail("derp_isp_stage: sharpening does not run with this config (a zero component)");
+        return create_fail("derp_isp_stage: sharpening does not run with this config (a zero component)");
       }
       src = stage == DERP_ISP_STAGE_LOWPASS ? s->lp.p : s->shp.p;
       bytes = 3 * plane;
       break;
-    default: return isp_fail("derp_isp_stage: no such stage " + std::to_string(stage));
+    default: return create_fail("derp_isp_stage: no such stage " + std::to_string(stage));
   }
-  ISPCHK(hipSetDevice(s->device));
-  ISPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int derp_isp_tables(const derp_isp* s, float* vignette_h, float* vignette_v, float* ccm9, float* tone_lut) {
   if (!s) {
-    return isp_fail("derp_isp_tables: bad arguments");
+    return create_fail("derp_isp_tables: bad arguments");
   }
   if (vignette_h) {
     memcpy(vignette_h, s->vigH.data(), s->vigH.size() * sizeof(float));

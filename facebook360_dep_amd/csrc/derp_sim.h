@@ -163,37 +163,24 @@ struct derp_sim {
   // supersampled planes of the last render; index 1 = the right eye of a stereo equirect
   DevBuf origin[2], dir, hit[2], dist[2], color[2], aux[2], small3[2], small1;
   int W = 0, H = 0, eyes = 0;
+  std::string* errSink() const {  // every derp_sim_* call reports through derp_last_error(nullptr)
+    return &g_create_error;
+  }
 };
 
 namespace {
 
-int sim_fail(const std::string& m) {
-  g_create_error = m;
-  return 1;
-}
-#define SIMCHK(expr)                                                           \
-  do {                                                                         \
-    const hipError_t e_ = (expr);                                              \
-    if (e_ != hipSuccess) {                                                    \
-      return sim_fail(std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-    }                                                                          \
-  } while (0)
-
 constexpr size_t kSimMaxRays = (size_t)1 << 28;  // rays of one render: 3 floats each stay far below 2^32 bytes per plane
-
-unsigned sim_blocks(size_t n) {
-  return (unsigned)((n + kSimBlock - 1) / kSimBlock);
-}
 
 int sim_alloc(derp_sim* s, int W, int H, int eyes) {
   const size_t n = (size_t)W * H;
   if (s->dir.ensure(n * 12)) {
-    return sim_fail("out of device memory");
+    return create_fail("out of device memory");
   }
   for (int e = 0; e < eyes; ++e) {
     if (s->origin[e].ensure(n * 12) || s->hit[e].ensure(n * 4) || s->dist[e].ensure(n * 4) || s->color[e].ensure(n * 12) ||
         s->aux[e].ensure(n * 4)) {
-      return sim_fail("out of device memory");
+      return create_fail("out of device memory");
     }
   }
   s->W = W;
@@ -204,10 +191,10 @@ int sim_alloc(derp_sim* s, int W, int H, int eyes) {
 
 int sim_trace(derp_sim* s, int eye, int invDepth) {
   const size_t n = (size_t)s->W * s->H;
-  k_sim_trace<<<sim_blocks(n), kSimBlock, 0, s->stream>>>(s->scene, s->origin[eye].as<float>(), s->dir.as<float>(), n, invDepth,
-                                                          s->hit[eye].as<int>(), s->dist[eye].as<float>(),
-                                                          s->color[eye].as<float>(), s->aux[eye].as<float>());
-  SIMCHK(hipGetLastError());
+  k_sim_trace<<<blocks_of(n, kSimBlock), kSimBlock, 0, s->stream>>>(s->scene, s->origin[eye].as<float>(), s->dir.as<float>(), n,
+                                                                    invDepth, s->hit[eye].as<int>(), s->dist[eye].as<float>(),
+                                                                    s->color[eye].as<float>(), s->aux[eye].as<float>());
+  KCHECK(s);
   return 0;
 }
 
@@ -216,7 +203,7 @@ int sim_trace(derp_sim* s, int eye, int invDepth) {
 int sim_downscale(derp_sim* s, int kind, const DevBuf& src, int w, int h, int aas, DevBuf& dst, float* out) {
   const size_t bytes = (size_t)w * h * (kind == 3 ? 12 : 4);
   if (dst.ensure(bytes)) {
-    return sim_fail("out of device memory");
+    return create_fail("out of device memory");
   }
   const AreaAxis ax{nullptr, nullptr, nullptr, aas};
   const dim3 g = grid2d(w, h, 1, kBlk2d);
@@ -225,17 +212,17 @@ int sim_downscale(derp_sim* s, int kind, const DevBuf& src, int w, int h, int aa
   } else {
     hipLaunchKernelGGL(k_resize_area<2>, g, kBlk2d, 0, s->stream, (const void*)src.p, w * aas, h * aas, dst.p, w, h, ax, ax, -1);
   }
-  SIMCHK(hipGetLastError());
-  SIMCHK(hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, s->stream));
+  KCHECK(s);
+  HIPCHK(s, hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, s->stream));
   return 0;
 }
 
 int sim_check_render(derp_sim* s, int w, int h, int aas) {
   if (!s->haveScene) {
-    return sim_fail("derp_sim: no scene was uploaded");
+    return create_fail("derp_sim: no scene was uploaded");
   }
   if (w <= 0 || h <= 0 || aas < 1 || aas > 64 || (size_t)w * aas * h * aas > kSimMaxRays) {
-    return sim_fail("derp_sim: bad image size or anti_alias_supersample (at most 2^28 rays per image)");
+    return create_fail("derp_sim: bad image size or anti_alias_supersample (at most 2^28 rays per image)");
   }
   return 0;
 }
@@ -247,30 +234,18 @@ int derp_sim_create(derp_sim** out, int device) {
     return 1;
   }
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-    return sim_fail("no HIP device present: the simulator's tracer has no CPU fallback");
-  }
-  if (device < 0 || device >= count) {
-    return sim_fail("HIP device index out of range");
-  }
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) {
-    return sim_fail("hipGetDeviceProperties failed");
-  }
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !getenv("DERP_ALLOW_ANY_ARCH")) {
-    return sim_fail(std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-  }
-  SIMCHK(hipSetDevice(device));
+  TRY(open_device(device, "the simulator's tracer", &prop));
   std::unique_ptr<derp_sim> owner(new derp_sim);
-  owner->device = device;
+  derp_sim* s = owner.get();
+  s->device = device;
   uint8_t perm[512];
   derp_sim_perlin_table(perm);
-  if (owner->perm.ensure(sizeof perm)) {
-    return sim_fail("out of device memory");
+  if (s->perm.ensure(sizeof perm)) {
+    return create_fail("out of device memory");
   }
-  SIMCHK(hipMemcpy(owner->perm.p, perm, sizeof perm, hipMemcpyHostToDevice));
-  SIMCHK(hipStreamCreateWithFlags(&owner->stream, hipStreamNonBlocking));
+  HIPCHK(s, hipMemcpy(s->perm.p, perm, sizeof perm, hipMemcpyHostToDevice));
+  HIPCHK(s, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   *out = owner.release();
   return 0;
 }
@@ -291,40 +266,40 @@ int derp_sim_upload(derp_sim* s, const derp_sim_triangle* triangles, int n_trian
   if (!s || !nodes || n_nodes < 1 || n_triangles < 0 || n_leaf_indices < 0 || (n_triangles > 0 && !triangles) ||
       (n_leaf_indices > 0 && !leaf_indices) || !skybox_bgr || sky_w <= 0 || sky_h <= 0 || !params ||
       (ceiling_bgr && (ceiling_w <= 0 || ceiling_h <= 0))) {
-    return sim_fail("derp_sim_upload: bad arguments");
+    return create_fail("derp_sim_upload: bad arguments");
   }
   // the walk trusts the tree: every link must move forward and every leaf must stay inside the lists
   for (int i = 0; i < n_nodes; ++i) {
     const derp_sim_node& nd = nodes[i];
     if (nd.skip <= i || nd.skip > n_nodes || nd.count < -1 ||
         (nd.count > 0 && (nd.first < 0 || (int64_t)nd.first + nd.count > n_leaf_indices))) {
-      return sim_fail("derp_sim_upload: node " + std::to_string(i) + " has a bad skip link or leaf range");
+      return create_fail("derp_sim_upload: node " + std::to_string(i) + " has a bad skip link or leaf range");
     }
   }
   for (int i = 0; i < n_leaf_indices; ++i) {
     if (leaf_indices[i] < 0 || leaf_indices[i] >= n_triangles) {
-      return sim_fail("derp_sim_upload: leaf index out of range");
+      return create_fail("derp_sim_upload: leaf index out of range");
     }
   }
-  SIMCHK(hipSetDevice(s->device));
+  HIPCHK(s, hipSetDevice(s->device));
   s->haveScene = false;
   const size_t tb = std::max<size_t>(1, n_triangles) * sizeof(derp_sim_triangle), nb = (size_t)n_nodes * sizeof(derp_sim_node),
                lb = std::max<size_t>(1, n_leaf_indices) * 4, sb = (size_t)sky_w * sky_h * 3,
                cb = ceiling_bgr ? (size_t)ceiling_w * ceiling_h * 3 : 0;
-  SIMCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipStreamSynchronize(s->stream));
   if (s->tris.ensure(tb) || s->nodes.ensure(nb) || s->leaf.ensure(lb) || s->sky.ensure(sb) || (cb && s->ceiling.ensure(cb))) {
-    return sim_fail("out of device memory");
+    return create_fail("out of device memory");
   }
   if (n_triangles > 0) {
-    SIMCHK(hipMemcpy(s->tris.p, triangles, (size_t)n_triangles * sizeof(derp_sim_triangle), hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(s->tris.p, triangles, (size_t)n_triangles * sizeof(derp_sim_triangle), hipMemcpyHostToDevice));
   }
-  SIMCHK(hipMemcpy(s->nodes.p, nodes, nb, hipMemcpyHostToDevice));
+  HIPCHK(s, hipMemcpy(s->nodes.p, nodes, nb, hipMemcpyHostToDevice));
   if (n_leaf_indices > 0) {
-    SIMCHK(hipMemcpy(s->leaf.p, leaf_indices, (size_t)n_leaf_indices * 4, hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(s->leaf.p, leaf_indices, (size_t)n_leaf_indices * 4, hipMemcpyHostToDevice));
   }
-  SIMCHK(hipMemcpy(s->sky.p, skybox_bgr, sb, hipMemcpyHostToDevice));
+  HIPCHK(s, hipMemcpy(s->sky.p, skybox_bgr, sb, hipMemcpyHostToDevice));
   if (cb) {
-    SIMCHK(hipMemcpy(s->ceiling.p, ceiling_bgr, cb, hipMemcpyHostToDevice));
+    HIPCHK(s, hipMemcpy(s->ceiling.p, ceiling_bgr, cb, hipMemcpyHostToDevice));
   }
   SimScene& S = s->scene;
   S.tris = s->tris.as<derp_sim_triangle>();
@@ -349,41 +324,42 @@ int derp_sim_upload(derp_sim* s, const derp_sim_triangle* triangles, int n_trian
 
 int derp_sim_render_camera(derp_sim* s, const derp_camera_desc* cam, int aas, float* bgr_out, float* depth_out) {
   if (!s || !cam || !bgr_out || !depth_out) {
-    return sim_fail("derp_sim_render_camera: bad arguments");
+    return create_fail("derp_sim_render_camera: bad arguments");
   }
   const int w = (int)cam->resolution[0], h = (int)cam->resolution[1];
   TRY(sim_check_render(s, w, h, aas));
   Cam c;
   if (const char* why = host_prepare_camera(*cam, c)) {
-    return sim_fail(std::string("camera ") + cam->id + ": " + why);
+    return create_fail(std::string("camera ") + cam->id + ": " + why);
   }
-  SIMCHK(hipSetDevice(s->device));
+  HIPCHK(s, hipSetDevice(s->device));
   TRY(sim_alloc(s, w * aas, h * aas, 1));
   const size_t n = (size_t)s->W * s->H;
   // the camera as the rig file holds it, in pixels: Camera::rescale to its own resolution changes nothing
-  k_sim_camera_rays<<<sim_blocks(n), kSimBlock, 0, s->stream>>>(c, scaled_cam(*cam, w, h), s->W, s->H, aas,
-                                                                s->origin[0].as<float>(), s->dir.as<float>(), s->hit[0].as<int>());
-  SIMCHK(hipGetLastError());
+  k_sim_camera_rays<<<blocks_of(n, kSimBlock), kSimBlock, 0, s->stream>>>(c, scaled_cam(*cam, w, h), s->W, s->H, aas,
+                                                                          s->origin[0].as<float>(), s->dir.as<float>(),
+                                                                          s->hit[0].as<int>());
+  KCHECK(s);
   TRY(sim_trace(s, 0, 0));
   TRY(sim_downscale(s, 3, s->color[0], w, h, aas, s->small3[0], bgr_out));
   TRY(sim_downscale(s, 2, s->aux[0], w, h, aas, s->small1, depth_out));
-  SIMCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipStreamSynchronize(s->stream));
   return 0;
 }
 
 int derp_sim_render_equirect(derp_sim* s, int w, int h, int aas, int stereo, double interpupillary_radius, float* bgr_a,
                              float* bgr_b, float* aux_out) {
   if (!s || !bgr_a || (stereo ? !bgr_b : !aux_out)) {
-    return sim_fail("derp_sim_render_equirect: bad arguments");
+    return create_fail("derp_sim_render_equirect: bad arguments");
   }
   TRY(sim_check_render(s, w, h, aas));
-  SIMCHK(hipSetDevice(s->device));
+  HIPCHK(s, hipSetDevice(s->device));
   TRY(sim_alloc(s, w * aas, h * aas, stereo ? 2 : 1));
   const size_t n = (size_t)s->W * s->H;
-  k_sim_equirect_rays<<<sim_blocks(n), kSimBlock, 0, s->stream>>>(s->W, s->H, stereo ? 1 : 0, interpupillary_radius,
-                                                                  s->origin[0].as<float>(), s->origin[1].as<float>(),
-                                                                  s->dir.as<float>(), s->hit[0].as<int>(), s->hit[1].as<int>());
-  SIMCHK(hipGetLastError());
+  k_sim_equirect_rays<<<blocks_of(n, kSimBlock), kSimBlock, 0, s->stream>>>(
+      s->W, s->H, stereo ? 1 : 0, interpupillary_radius, s->origin[0].as<float>(), s->origin[1].as<float>(), s->dir.as<float>(),
+      s->hit[0].as<int>(), s->hit[1].as<int>());
+  KCHECK(s);
   TRY(sim_trace(s, 0, 1));
   TRY(sim_downscale(s, 3, s->color[0], w, h, aas, s->small3[0], bgr_a));
   if (stereo) {
@@ -392,16 +368,16 @@ int derp_sim_render_equirect(derp_sim* s, int w, int h, int aas, int stereo, dou
   } else {
     TRY(sim_downscale(s, 2, s->aux[0], w, h, aas, s->small1, aux_out));
   }
-  SIMCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(s, hipStreamSynchronize(s->stream));
   return 0;
 }
 
 int derp_sim_trace_rays(derp_sim* s, const float* rays6, size_t n) {
   if (!s || !rays6 || n == 0 || n > (size_t)INT32_MAX) {
-    return sim_fail("derp_sim_trace_rays: bad arguments");
+    return create_fail("derp_sim_trace_rays: bad arguments");
   }
   TRY(sim_check_render(s, (int)n, 1, 1));
-  SIMCHK(hipSetDevice(s->device));
+  HIPCHK(s, hipSetDevice(s->device));
   TRY(sim_alloc(s, (int)n, 1, 1));
   std::vector<float> o(3 * n), d(3 * n);
   for (size_t i = 0; i < n; ++i) {
@@ -410,17 +386,17 @@ int derp_sim_trace_rays(derp_sim* s, const float* rays6, size_t n) {
       d[3 * i + k] = rays6[6 * i + 3 + k];
     }
   }
-  SIMCHK(hipMemcpyAsync(s->origin[0].p, o.data(), n * 12, hipMemcpyHostToDevice, s->stream));
-  SIMCHK(hipMemcpyAsync(s->dir.p, d.data(), n * 12, hipMemcpyHostToDevice, s->stream));
-  SIMCHK(hipMemsetAsync(s->hit[0].p, 0xff, n * 4, s->stream));  // -1: not outside
+  HIPCHK(s, hipMemcpyAsync(s->origin[0].p, o.data(), n * 12, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemcpyAsync(s->dir.p, d.data(), n * 12, hipMemcpyHostToDevice, s->stream));
+  HIPCHK(s, hipMemsetAsync(s->hit[0].p, 0xff, n * 4, s->stream));  // -1: not outside
   TRY(sim_trace(s, 0, 0));
-  SIMCHK(hipStreamSynchronize(s->stream));  // (the host vectors go out of scope)
+  HIPCHK(s, hipStreamSynchronize(s->stream));  // (the host vectors go out of scope)
   return 0;
 }
 
 int derp_sim_stage_size(const derp_sim* s, int* width, int* height) {
   if (!s || !width || !height) {
-    return sim_fail("derp_sim_stage_size: bad arguments");
+    return create_fail("derp_sim_stage_size: bad arguments");
   }
   *width = s->W;
   *height = s->H;
@@ -429,10 +405,10 @@ int derp_sim_stage_size(const derp_sim* s, int* width, int* height) {
 
 int derp_sim_stage(derp_sim* s, int stage, int eye, void* out) {
   if (!s || !out) {
-    return sim_fail("derp_sim_stage: bad arguments");
+    return create_fail("derp_sim_stage: bad arguments");
   }
   if (s->eyes == 0 || eye < 0 || eye >= s->eyes) {
-    return sim_fail("derp_sim_stage: nothing was rendered yet for this eye");
+    return create_fail("derp_sim_stage: nothing was rendered yet for this eye");
   }
   const size_t n = (size_t)s->W * s->H;
   const void* src = nullptr;
@@ -443,9 +419,9 @@ int derp_sim_stage(derp_sim* s, int stage, int eye, void* out) {
     case DERP_SIM_STAGE_HIT: src = s->hit[eye].p; break;
     case DERP_SIM_STAGE_DISTANCE: src = s->dist[eye].p; break;
     case DERP_SIM_STAGE_COLOR: src = s->color[eye].p, bytes = n * 12; break;
-    default: return sim_fail("derp_sim_stage: no such stage " + std::to_string(stage));
+    default: return create_fail("derp_sim_stage: no such stage " + std::to_string(stage));
   }
-  SIMCHK(hipSetDevice(s->device));
-  SIMCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(s, hipSetDevice(s->device));
+  HIPCHK(s, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
   return 0;
 }

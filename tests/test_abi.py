@@ -40,6 +40,30 @@ def test_no_cpu_fallback(built):
         raise AssertionError("derp_create succeeded without a GPU")
 
 
+def test_every_create_refuses_a_missing_device(built):
+    """derp_create, derp_isp_create and derp_sim_create share one device check: without a HIP device each fails, hands
+    back no handle and leaves "no HIP device" (and which path has no CPU fallback) in derp_last_error(NULL)."""
+    import ctypes as C
+
+    import torch
+
+    from facebook360_dep_amd import derp, synth
+
+    if torch.cuda.is_available():
+        return
+    lib = derp.lib()
+    cams = (derp.CameraDesc * 2)(*[derp.camera_desc(c) for c in synth.make_rig(2, 64)["cameras"]])
+    cfg = derp.isp_config({"width": 8, "height": 6})
+    creates = (("the depth path", lambda h: lib.derp_create(C.byref(h), 0, cams, 2, cams, 2)),
+               ("the ISP", lambda h: lib.derp_isp_create(C.byref(h), 0, C.byref(cfg), 0, 1, 1)),
+               ("the simulator's tracer", lambda h: lib.derp_sim_create(C.byref(h), 0)))
+    for path, create in creates:
+        h = C.c_void_p()
+        assert create(h) != 0 and not h.value, path
+        message = lib.derp_last_error(None).decode()
+        assert "no HIP device" in message and path in message and "no CPU fallback" in message, message
+
+
 def test_product_does_not_touch_oracle():
     """The product package and the CLI sources never import / link the oracle."""
     pkg = os.path.join(ROOT, "facebook360_dep_amd")
