@@ -568,9 +568,13 @@ int bilateral_radius(int level) {  // Derp.cpp:876-878
 
 size_t bilateral_lds_bytes(int radius) {
   // rows of the tile are padded to a multiple of 16 texels (k_joint_bilateral: bank-conflict-free float4 reads)
-  const size_t t = (size_t)((16 + 2 * radius + 15) & ~15) * (16 + 2 * radius);
+  const size_t side = 16 + 2 * (size_t)radius;
+  const size_t t = ((side + 15) & ~(size_t)15) * side;
   return t * 4 * sizeof(float) + ((t + 3) & ~(size_t)3);
 }
+
+// what a block of k_joint_bilateral may ask for: 64 KiB less the kernel's own 256 B (its exp table)
+constexpr size_t kBilateralMaxLds = 64 * 1024 - 256;
 
 int run_bilateral(derp_ctx* c) {
   const int L = c->cur;

@@ -122,10 +122,27 @@ int derp_upsample_disparity(derp_ctx* c, int d, const float* disp, int w, int h,
   return download_sync(c, out, res.p, nu * 4);
 }
 
+// The tiled kernel while its tile fits the 64 KiB of LDS a block may have (radius <= 22: 65 280 B plus the kernel's
+// 256 B exp table), the untiled one beyond: the same bits either way, so no radius is refused (UpsampleDisparity's is
+// scale^2 + 1, UpsampleDisparityLib.cpp:93-96).
+template <bool GUIDE_U16>
+static void launch_joint_bilateral(derp_ctx* c, const float* image, const void* guide, const uint8_t* mask, int w, int h,
+                                   int radius, float sigma, float w0, float w1, float w2, float* out) {
+  const size_t n = (size_t)w * h;
+  const dim3 grid((w + 15) / 16, (h + 15) / 16, 1);
+  if (bilateral_lds_bytes(radius) <= kBilateralMaxLds) {
+    hipLaunchKernelGGL(k_joint_bilateral<GUIDE_U16>, grid, dim3(256), bilateral_lds_bytes(radius), c->stream, image, guide,
+                       mask, w, h, radius, sigma, w0, w1, w2, out, n, n, (const int*)nullptr);
+  } else {
+    hipLaunchKernelGGL(k_joint_bilateral_direct<GUIDE_U16>, grid, dim3(256), 0, c->stream, image, guide, mask, w, h,
+                       radius, sigma, w0, w1, w2, out);
+  }
+}
+
 int derp_joint_bilateral_u16(derp_ctx* c, const float* image, const uint16_t* guide, const uint8_t* mask, int w, int h,
                              int radius, float sigma, float w0, float w1, float w2, float* out) {
-  if (!c || !image || !guide || !mask || !out || radius < 0 || bilateral_lds_bytes(radius) > 64 * 1024) {
-    return fail(c, "bad arguments (radius must be in [0, 47])");
+  if (!c || !image || !guide || !mask || !out || w <= 0 || h <= 0 || radius < 0 || radius > (1 << 30)) {
+    return fail(c, "bad arguments (radius must be in [0, 2^30])");
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
@@ -136,16 +153,15 @@ int derp_joint_bilateral_u16(derp_ctx* c, const float* image, const uint16_t* gu
   ALLOC(c, g4, n * 8);
   ALLOC(c, res, n * 4);
   hipLaunchKernelGGL(k_bgr_to_bgrx, dim3(flat_grid(n)), dim3(256), 0, c->stream, g3.as<uint16_t>(), g4.as<ushort4>(), n);
-  hipLaunchKernelGGL(k_joint_bilateral<true>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
-                     bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g4.as<ushort4>(),
-                     m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
+  launch_joint_bilateral<true>(c, im.as<float>(), (const void*)g4.as<ushort4>(), m.as<uint8_t>(), w, h, radius, sigma, w0,
+                               w1, w2, res.as<float>());
   return download_sync(c, out, res.p, n * 4);
 }
 
 int derp_joint_bilateral_f32(derp_ctx* c, const float* image, const float* guide, const uint8_t* mask, int w, int h,
                              int radius, float sigma, float w0, float w1, float w2, float* out) {
-  if (!c || !image || !guide || !mask || !out || radius < 0 || bilateral_lds_bytes(radius) > 64 * 1024) {
-    return fail(c, "bad arguments (radius must be in [0, 47])");
+  if (!c || !image || !guide || !mask || !out || w <= 0 || h <= 0 || radius < 0 || radius > (1 << 30)) {
+    return fail(c, "bad arguments (radius must be in [0, 2^30])");
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)w * h;
@@ -154,9 +170,8 @@ int derp_joint_bilateral_f32(derp_ctx* c, const float* image, const float* guide
   TRY(upload_sync(c, g, guide, n * 12));
   TRY(upload_sync(c, m, mask, n));
   ALLOC(c, res, n * 4);
-  hipLaunchKernelGGL(k_joint_bilateral<false>, dim3((w + 15) / 16, (h + 15) / 16, 1), dim3(256),
-                     bilateral_lds_bytes(radius), c->stream, im.as<float>(), (const void*)g.as<float>(),
-                     m.as<uint8_t>(), w, h, radius, sigma, w0, w1, w2, res.as<float>(), n, n, (const int*)nullptr);
+  launch_joint_bilateral<false>(c, im.as<float>(), (const void*)g.as<float>(), m.as<uint8_t>(), w, h, radius, sigma, w0, w1,
+                                w2, res.as<float>());
   return download_sync(c, out, res.p, n * 4);
 }
 

@@ -2220,6 +2220,30 @@ __device__ __forceinline__ float expf_glibc(float x, const unsigned long long* t
 // skip and the float accumulation are the reference's.
 //   GUIDE_U16 = true : guide is BGRX u16 (TGuide = Vec3w, factor 1/65535)   — Derp.cpp:875-902
 //   GUIDE_U16 = false: guide is 3 x f32 (TGuide = Vec3f, factor 1)          — UpsampleDisparity.cpp:109-128
+// one texel's record: the guide colour scaled by the reference's factor, and the image value
+template <bool GUIDE_U16>
+__device__ __forceinline__ float4 bilateral_texel(const void* __restrict__ guideV, size_t j, float value) {
+  if (GUIDE_U16) {
+    const ushort4 g = reinterpret_cast<const ushort4*>(guideV)[j];
+    const float factor = 1 / 65535.0f;
+    return make_float4(g.x * factor, g.y * factor, g.z * factor, value);
+  }
+  const float* g = reinterpret_cast<const float*>(guideV) + j * 3;
+  const float factor = 1 / 1.0f;
+  return make_float4(g[0] * factor, g[1] * factor, g[2] * factor, value);
+}
+
+// one unmasked tap: weight = exp((-colorDiffSq / 3.0f) / denom), both quotients through their fp64 reciprocals
+__device__ __forceinline__ void bilateral_tap(float4 centre, float4 t, float weight0, float weight1, float weight2,
+                                              double rcpDenom, const unsigned long long* expTab, float& sumWeight,
+                                              float& weightedAvg) {
+  const float d0 = centre.x - t.x, d1 = centre.y - t.y, d2 = centre.z - t.z;
+  const float colorDiffSq = weight0 * (d0 * d0) + weight1 * (d1 * d1) + weight2 * (d2 * d2);
+  const float weight = expf_glibc(div_by_const(div_by_const(-colorDiffSq, 1.0 / 3.0), rcpDenom), expTab);
+  sumWeight += weight;
+  weightedAvg += weight * t.w;
+}
+
 template <bool GUIDE_U16>
 __global__ void __launch_bounds__(256)
     k_joint_bilateral(const float* __restrict__ image, const void* __restrict__ guideV,
@@ -2252,15 +2276,7 @@ __global__ void __launch_bounds__(256)
     const int sx = min(max(x0 + tx, 0), W - 1), sy = min(max(y0 + ty, 0), H - 1);
     const size_t j = (size_t)sy * W + sx;
     tMask[i] = m[j];
-    if (GUIDE_U16) {
-      const ushort4 g = reinterpret_cast<const ushort4*>(guideV)[gplane + j];
-      const float factor = 1 / 65535.0f;
-      tTex[i] = make_float4(g.x * factor, g.y * factor, g.z * factor, img[j]);
-    } else {
-      const float* g = reinterpret_cast<const float*>(guideV) + (gplane + j) * 3;
-      const float factor = 1 / 1.0f;
-      tTex[i] = make_float4(g[0] * factor, g[1] * factor, g[2] * factor, img[j]);
-    }
+    tTex[i] = bilateral_texel<GUIDE_U16>(guideV, gplane + j, img[j]);
   }
   __syncthreads();
   const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
@@ -2272,9 +2288,8 @@ __global__ void __launch_bounds__(256)
   const float4 centre = tTex[c];
   float result = centre.w;
   if (tMask[c]) {
-    const float g0 = centre.x, g1 = centre.y, g2 = centre.z;
     const float denom = 2.0f * (sigma * sigma);
-    const double rcpDenom = 1.0 / (double)denom, rcp3 = 1.0 / 3.0;
+    const double rcpDenom = 1.0 / (double)denom;
     float sumWeight = 0.f, weightedAvg = 0.f;
     for (int v = -radius; v <= radius; ++v) {
       const int row = c + v * P;
@@ -2283,12 +2298,7 @@ __global__ void __launch_bounds__(256)
         if (!tMask[j]) {
           continue;
         }
-        const float4 t = tTex[j];
-        const float d0 = g0 - t.x, d1 = g1 - t.y, d2 = g2 - t.z;
-        const float colorDiffSq = weight0 * (d0 * d0) + weight1 * (d1 * d1) + weight2 * (d2 * d2);
-        const float weight = expf_glibc(div_by_const(div_by_const(-colorDiffSq, rcp3), rcpDenom), expTab);  // (-c / 3.0f) / denom
-        sumWeight += weight;
-        weightedAvg += weight * t.w;
+        bilateral_tap(centre, tTex[j], weight0, weight1, weight2, rcpDenom, expTab, sumWeight, weightedAvg);
       }
     }
     if (sumWeight != 0.0f) {
@@ -2296,6 +2306,49 @@ __global__ void __launch_bounds__(256)
     }
   }
   out[(size_t)p * planeStride + (size_t)y * W + x] = result;
+}
+
+// The same filter without the tile, for the radii whose tile does not fit the 64 KiB of LDS one block may have (radius
+// >= 23; the level loop's radii are <= 5, UpsampleDisparity's is scale^2 + 1 and has no limit in the reference): every
+// tap reads its texel from global memory at the clamped coordinates the tile would hold. Same records, same tap order,
+// same skip and the same float accumulation, hence the same bits. A correctness path: (2r+1)^2 x 3 global loads per pixel.
+template <bool GUIDE_U16>
+__global__ void __launch_bounds__(256)
+    k_joint_bilateral_direct(const float* __restrict__ image, const void* __restrict__ guideV,
+                             const uint8_t* __restrict__ mask, int W, int H, int radius, float sigma, float weight0,
+                             float weight1, float weight2, float* __restrict__ out) {
+  __shared__ unsigned long long expTab[32];
+  if (threadIdx.x < 32) {
+    expTab[threadIdx.x] = kExp2fTab[threadIdx.x];
+  }
+  __syncthreads();
+  const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+  if (x >= W || y >= H) {
+    return;
+  }
+  const size_t idx = (size_t)y * W + x;
+  float result = image[idx];
+  if (mask[idx]) {
+    const float4 centre = bilateral_texel<GUIDE_U16>(guideV, idx, result);
+    const float denom = 2.0f * (sigma * sigma);
+    const double rcpDenom = 1.0 / (double)denom;
+    float sumWeight = 0.f, weightedAvg = 0.f;
+    for (int v = -radius; v <= radius; ++v) {
+      const size_t row = (size_t)min(max(y + v, 0), H - 1) * W;
+      for (int u = -radius; u <= radius; ++u) {
+        const size_t j = row + min(max(x + u, 0), W - 1);
+        if (!mask[j]) {
+          continue;
+        }
+        bilateral_tap(centre, bilateral_texel<GUIDE_U16>(guideV, j, image[j]), weight0, weight1, weight2, rcpDenom,
+                      expTab, sumWeight, weightedAvg);
+      }
+    }
+    if (sumWeight != 0.0f) {
+      result = weightedAvg / sumWeight;
+    }
+  }
+  out[idx] = result;
 }
 
 // maskedMedianBlur — CvUtil.h:336-385; optional fused maskFov (Derp.cpp:940-951).

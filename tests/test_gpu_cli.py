@@ -670,6 +670,25 @@ def test_upsample_cli(dataset, tmp_path):
         ref = O.joint_bilateral_f32(ref, guide, np.ones((h_up, w_up), np.uint8), radius, 0.05, 0.5, 0.5, 1.0)
         got = dio.read_pfm(os.path.join(up_e, cam, "000000.pfm"))
         assert common.compare_disparity(got, ref, 1e-5)[0] == 0, cam
+    # (f) five times the width: a filter radius of int(5 * 5 + 1) = 26 (UpsampleDisparityLib.cpp:93-96), past the largest
+    # one whose tile fits in LDS, so the joint bilateral filter runs untiled. Level-2 disparities (48 px) to 240 px, the
+    # level-0 colour (96 px) enlarged as in (e). Bit for bit.
+    w_5, h_5 = 5 * dataset["sizes"][2][0], 5 * dataset["sizes"][2][1]
+    up_f = str(tmp_path / "up_f")
+    run("UpsampleDisparity", "--rig=" + rigf, "--disparity=" + lvl2, "--output=" + up_f, "--resolution=%d" % w_5,
+        "--color=" + color0)
+    for d, cam in enumerate(ids):
+        disp = dio.read_pfm(os.path.join(lvl2, cam, "000000.pfm"))
+        guide = O.cv_resize_area(fr["color"][0][d].astype(np.float32) * np.float32(1.0 / 65535.0), w_5, h_5)
+        radius = O.upsample_radius(disp.shape[1], w_5)
+        assert radius == 26 and disp.shape[1] * 5 == w_5
+        ref = O.upsample_disparity(rd, d, disp, w_5, h_5)
+        ref = O.joint_bilateral_f32(ref, guide, np.ones((h_5, w_5), np.uint8), radius, 0.05, 0.5, 0.5, 1.0)
+        got = dio.read_pfm(os.path.join(up_f, cam, "000000.pfm"))
+        assert got.shape == ref.shape
+        differ = int((~((got == ref) | (np.isnan(got) & np.isnan(ref)))).sum())
+        print("UpsampleDisparity x5 %s: %d differ" % (cam, differ))
+        assert differ == 0, (cam, differ)
 
 
 def test_layer_disparities_cli(dataset, tmp_path):

@@ -255,13 +255,12 @@ def test_filters(small, gpu):
     for radius in (1, 3, 5):
         ref = O.joint_bilateral_u16(clean, guide, mask, radius, 0.005, 0.5, 1.0, 1.0)
         got = gpu.joint_bilateral_u16(clean, guide, mask, radius, 0.005, 0.5, 1.0, 1.0)
-        bad, rel = common.compare_disparity(got, ref, 1e-5)
-        print("bilateral r=%d max rel %.3g bit-diff %d" % (radius, rel, _float_equal(got, ref)))
-        assert bad == 0, (radius, bad, rel)
+        print("bilateral r=%d bit-diff %d" % (radius, _float_equal(got, ref)))
+        assert _float_equal(got, ref) == 0, radius
     gf = (guide.astype(np.float32) / 65535.0)
     ref = O.joint_bilateral_f32(clean, gf, mask, 5, 0.05, 0.5, 0.5, 1.0)
     got = gpu.joint_bilateral_f32(clean, gf, mask, 5, 0.05, 0.5, 0.5, 1.0)
-    assert common.compare_disparity(got, ref, 1e-5)[0] == 0
+    assert _float_equal(got, ref) == 0
     bg = rng.random((h, w)).astype(np.float32)
     for background in (None, bg):
         ref = O.masked_median(disp, background, mask, 1)

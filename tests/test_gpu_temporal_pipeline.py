@@ -2,8 +2,9 @@
 tiled kernel's window loop software-pipelined (frame t + 1 loaded while frame t's taps run) — against the oracle's
 `temporal_filter`, bit for bit, for both kernels (`k_temporal_tiled`, and `k_temporal` through DERP_NO_TEMPORAL_TILE):
 clamped windows (the first and last frames of a sequence), masked pixels, windows longer than one launch's 31 frames (the
-carry path), sizes that are no multiple of the 32 x 8 block, and radii 1-3 (radius 3:
-a tile of more than 512 cells, whose tail is loaded outside the pipeline). With DERP_PARENT_LIB naming an earlier build of
+carry path), sizes that are no multiple of the 32 x 8 block, and radii 0-4, 16 and 17 (radius 3: a tile of more than
+512 cells, whose tail is loaded outside the pipeline; 16 and 17: the last radius whose tile fits in LDS and the first
+that does not). With DERP_PARENT_LIB naming an earlier build of
 the library, the same inputs go through it in a child process and must give the same bits too."""
 import os
 import subprocess
@@ -49,7 +50,27 @@ CASES = [  # seed, w, h, frames, radius, offsets of the filtered frame in the wi
     (3, 45, 29, 4, 3, (0, 3)),
     (4, 33, 9, 35, 1, (0, 17, 34)),  # two launches: the sums travel through the carry buffer
     (5, 5, 3, 3, 2, (1,)),  # smaller than the halo: every tap clamps
+    (6, 33, 9, 2, 0, (0, 1)),  # radius 0: one tap per frame, a tile without a halo
+    (7, 70, 20, 3, 4, (0, 2)),
+    (8, 33, 9, 3, 16, (0, 2)),  # the largest radius the tiled kernel takes: 2560 cells, ten passes of its tail loader
+    (9, 33, 9, 3, 17, (0, 2)),  # the smallest one that goes to the direct kernel either way
+    (10, 5, 3, 2, 16, (0, 1)),  # the same two radii on an image far smaller than the halo
+    (11, 5, 3, 2, 17, (0, 1)),
 ]
+
+
+def takes_tiled_kernel(radius):
+    """The host's choice restated (temporal_launch in csrc/derp_capi.hip): two LDS buffers of (32 + 2r) x (8 + 2r) cells
+    of 9 bytes, each rounded up to 16, must fit 48 KiB. The context does not report which kernel ran, so the formula is
+    what pins that the cases above sit on either side of the switch."""
+    return radius >= 0 and 2 * (((32 + 2 * radius) * (8 + 2 * radius) * 9 + 15) & ~15) <= 48 * 1024
+
+
+def test_cases_sit_on_both_sides_of_the_tiled_kernels_limit():
+    assert takes_tiled_kernel(16) and not takes_tiled_kernel(17)
+    assert 2 * (((32 + 32) * (8 + 32) * 9 + 15) & ~15) == 46080
+    radii = {c[4] for c in CASES}
+    assert {0, 16, 17} <= radii and all(takes_tiled_kernel(r) for r in radii if r <= 16)
 
 
 def _gpu(monkeypatch, direct):
