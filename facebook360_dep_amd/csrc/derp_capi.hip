@@ -118,7 +118,25 @@ LevelView make_view(derp_ctx* c, int stage, int dst0, int nd) {
   V.fovMask = c->w.fovMask.as<uint8_t>();
   V.pairCount = c->w.pairCount.as<uint8_t>();
   V.counters = counter_slot(c, stage, L);
+#if DERP_BLOCK_TRACE
+  V.blockTrace = nullptr;
+#endif
   return V;
+}
+// DERP_BLOCK_TRACE builds: the launch of random proposals (which = 0) / ping-pong (1) about to go out records its blocks
+int block_trace_attach(derp_ctx* c, LevelView& V, int which, int gridX, int gridY) {
+#if DERP_BLOCK_TRACE
+  DevBuf& buf = c->blockTrace[which][V.level];
+  const size_t bytes = (size_t)gridX * gridY * 2 * sizeof(unsigned long long);
+  ALLOC(c, buf, bytes);
+  HIPCHK(c, hipMemsetAsync(buf.as<unsigned long long>(), 0, bytes, c->stream));
+  V.blockTrace = buf.as<unsigned long long>();
+  c->blockTraceGrid[which][V.level][0] = gridX;
+  c->blockTraceGrid[which][V.level][1] = gridY;
+#else
+  (void)c, (void)V, (void)which, (void)gridX, (void)gridY;
+#endif
+  return 0;
 }
 
 // k_blur3_u16: 64 x 4 threads, each a column strip of kBlurRows rows
@@ -434,8 +452,38 @@ int tiles_of(int W, int H, int& tilesX) {
   return tilesX * tilesY * (256 / kCostBlock);
 }
 constexpr size_t kCostLdsPerSrc = (size_t)kCostBlock * sizeof(SsdPair);
-int round8(int n) {
-  return (n + 7) / 8 * 8;
+// How a launch of random proposals / ping-pong lays a level's `tiles` (tiles_of) over its blocks: the blocks of the
+// grid's x (a multiple of 8 * bands: xcd_swizzle), each walking `perBlock` consecutive tiles. Tile indices at or past
+// `tiles` fall below the image (tile_pixel) and do nothing.
+struct CostGrid {
+  int blocks, bands, perBlock;
+};
+// bands (K), random proposals (`spread`): as many as leave a run no shorter than one row of kTileBlock squares (tilesX * 4 *
+// kTileBlock wave tiles: thinner runs would widen what an XCD's L2 serves at one time), at most kCostMaxBands. Their gate
+// passes the pixels unevenly over the image, and with one band each the XCDs' shares differ. Ping-pong: 1. Its XCDs end
+// within 1 % of one another as it is, and four bands cost its level-0 launch 1 % (profiles/r13_cost_tile_order.txt).
+// perBlock (N): 1. The kernels that walk N > 1 tiles spill (the level's scalars stay live around the tile loop) and are a
+// quarter slower; they stay for the A/B. DERP_XCD_BANDS / DERP_COST_TILES_PER_BLOCK force K / N for both kernels.
+constexpr int kCostMaxBands = 4, kCostMaxTilesPerBlock = 4;
+int cost_grid_blocks(int tiles, int bands, int perBlock) {
+  const int items = (tiles + perBlock - 1) / perBlock, unit = 8 * bands;
+  return (items + unit - 1) / unit * unit;
+}
+CostGrid cost_grid(const derp_ctx* c, int tiles, int tilesX, bool spread) {
+  const auto pow2_floor = [](int v, int cap) {
+    int p = 1;
+    while (p * 2 <= std::min(v, cap)) {
+      p *= 2;
+    }
+    return p;
+  };
+  CostGrid g;
+  g.perBlock = c->costTilesPerBlock > 0 ? pow2_floor(c->costTilesPerBlock, kCostMaxTilesPerBlock) : 1;
+  const int rowOfSquares = tilesX * (256 / kCostBlock) * kTileBlock;
+  g.bands = c->xcdBands > 0 ? pow2_floor(c->xcdBands, kCostMaxBands)
+                            : spread ? pow2_floor(std::max(1, tiles / (8 * rowOfSquares)), kCostMaxBands) : 1;
+  g.blocks = cost_grid_blocks(tiles, g.bands, g.perBlock);
+  return g;
 }
 // dynamic LDS of a one-wave block such that at most `waves` blocks per SIMD (4 x waves per CU) fit a CU's LDS
 // (`ldsPerCu`: hipDeviceProp.maxSharedMemoryPerMultiProcessor, 160 KB on gfx950); `fixed` = the kernel's static LDS
@@ -497,8 +545,12 @@ int run_random_proposals(derp_ctx* c, int dst0, int nd) {
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->randomWaves, c->ldsPerCu, kCostLdsStatic);
-  hipLaunchKernelGGL(cost_four_waves(c) ? k_random_proposals : k_random_proposals_w3, dim3(round8(tiles), nd),
-                     dim3(kCostBlock), lds, c->stream, V, c->w.rank.as<int>(), tilesX, tiles);
+  const CostGrid cg = cost_grid(c, tiles, tilesX, true);
+  TRY(block_trace_attach(c, V, 0, cg.blocks, nd));
+  const bool four = cost_four_waves(c);
+  const auto kernel = cg.perBlock > 1 ? (four ? k_random_proposals_walk : k_random_proposals_walk_w3)
+                                      : (four ? k_random_proposals : k_random_proposals_w3);
+  hipLaunchKernelGGL(kernel, dim3(cg.blocks, nd), dim3(kCostBlock), lds, c->stream, V, c->w.rank.as<int>(), tilesX, cg.bands, cg.perBlock);
   KCHECK(c);
   return 0;
 }
@@ -516,11 +568,15 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->ppWaves, c->ldsPerCu, kCostLdsStatic);
   const bool four = cost_four_waves(c);
-  const auto kernel = c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3);
+  const CostGrid cg = cost_grid(c, tiles, tilesX, false);
+  const auto kernel = cg.perBlock > 1
+                          ? (c->ppCompact ? (four ? k_ping_pong_walk : k_ping_pong_walk_w3) : (four ? k_ping_pong_loop_walk : k_ping_pong_loop_walk_w3))
+                          : (c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3));
+  TRY(block_trace_attach(c, V, 1, cg.blocks, nd));
   for (int it = 1; it <= c->opt.ping_pong_iterations; ++it) {
-    hipLaunchKernelGGL(kernel, dim3(round8(tiles), nd), dim3(kCostBlock), lds,
+    hipLaunchKernelGGL(kernel, dim3(cg.blocks, nd), dim3(kCostBlock), lds,
                        c->stream, V, c->w.changed.as<uint8_t>(), c->w.dispRes.as<float>(), c->w.costRes.as<float>(), tilesX,
-                       (int)(it == 1 && c->randomRanThisLevel && !c->noMemo));
+                       (int)(it == 1 && c->randomRanThisLevel && !c->noMemo), cg.bands, cg.perBlock);
     KCHECK(c);
     hipLaunchKernelGGL(k_ping_pong_commit, dim3(flat_grid(n * nd)), dim3(256), 0, c->stream,
                        c->w.disparity.as<float>() + (size_t)dst0 * n, c->w.cost.as<float>() + (size_t)dst0 * n,
@@ -977,6 +1033,12 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
   }
   if (const char* e = getenv("DERP_XCD_ROTATE")) {
     c->xcdRotate = atoi(e);
+  }
+  if (const char* e = getenv("DERP_XCD_BANDS")) {
+    c->xcdBands = atoi(e);
+  }
+  if (const char* e = getenv("DERP_COST_TILES_PER_BLOCK")) {
+    c->costTilesPerBlock = atoi(e);
   }
   c->noMemo = getenv("DERP_NO_MEMO") != nullptr;
   if (const char* e = getenv("DERP_PP_COMPACT")) {

@@ -135,6 +135,13 @@ struct derp_ctx {
   double accMs[ST_COUNT][kMaxLevels] = {};
   int accLaunch[ST_COUNT][kMaxLevels] = {};
   int xcdRotate = 1;
+  // random proposals' / ping-pong's tile order (cost_grid): bands per XCD and tiles per block, 0 = the launcher's rule
+  // (DERP_XCD_BANDS / DERP_COST_TILES_PER_BLOCK, developer A/B switches; same results), read once in derp_create
+  int xcdBands = 0, costTilesPerBlock = 0;
+  // DERP_BLOCK_TRACE builds (tools/block_trace.py): {start, end} of every block of the last random-proposal [0] /
+  // ping-pong [1] launch of a level, and that launch's grid (x, y)
+  DevBuf blockTrace[2][kMaxLevels];
+  int blockTraceGrid[2][kMaxLevels][2] = {};
   bool noMemo = false;  // DERP_NO_MEMO (developer switch), read once in derp_create
   // ping-pong's candidate loop: compacted into full waves of (pixel, candidate) tasks, or one pixel per lane
   // (DERP_PP_COMPACT=0, developer A/B switch; same results), read once in derp_create

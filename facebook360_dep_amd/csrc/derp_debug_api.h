@@ -271,6 +271,29 @@ int derp_profile_memoised(derp_ctx* c, const char* stage, int level, uint64_t* n
   *n_memoised = m;
   return 0;
 }
+int derp_debug_block_trace(derp_ctx* c, const char* stage, int level, uint64_t* out, size_t capacity, int* grid_x, int* grid_y) {
+  if (!c || !stage || !grid_x || !grid_y || level < 0 || level >= kMaxLevels) {
+    return fail(c, "bad arguments");
+  }
+#if DERP_BLOCK_TRACE
+  const int which = strcmp(stage, "random_proposals") == 0 ? 0 : strcmp(stage, "ping_pong") == 0 ? 1 : -1;
+  if (which < 0) {
+    return fail(c, "no block trace of stage '%s'", stage);
+  }
+  *grid_x = c->blockTraceGrid[which][level][0];
+  *grid_y = c->blockTraceGrid[which][level][1];
+  const size_t n = (size_t)*grid_x * *grid_y * 2;
+  if (!out || capacity < n) {
+    return 0;  // (the size query)
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->blockTrace[which][level].as<unsigned long long>(), n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return 0;
+#else
+  (void)out, (void)capacity;
+  return fail(c, "this library records no block trace: build it with -DDERP_BLOCK_TRACE=1 (tools/block_trace.py)");
+#endif
+}
 int derp_device_memory(derp_ctx* c, uint64_t* free_bytes, uint64_t* total_bytes) {
   TRY(use_device(c));
   size_t f = 0, t = 0;
@@ -304,4 +327,22 @@ int derp_host_nth_element_pairs(float* pairs, int n, int nth) {
 float derp_host_minstd_uniform(int seed, uint64_t draw_index, float a, float b) {
   uint32_t state = minstd_jump(minstd_seed(seed), draw_index);
   return minstd_uniform(state, a, b);
+}
+// the tile order of a random-proposal / ping-pong launch over `tiles` tiles as the kernels compute it: out[b * per_block +
+// step] for every block b of the grid and step of its walk; returns the grid's block count (0: bad arguments or capacity)
+int derp_host_cost_tile_map(int tiles, int bands, int rot, int per_block, int* out, int capacity) {
+  const auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+  if (tiles <= 0 || !pow2(bands) || bands > kCostMaxBands || !pow2(per_block) || per_block > kCostMaxTilesPerBlock || !out) {
+    return 0;
+  }
+  const int blocks = cost_grid_blocks(tiles, bands, per_block);
+  if ((long long)blocks * per_block > capacity) {
+    return 0;
+  }
+  for (int b = 0; b < blocks; ++b) {
+    for (int step = 0; step < per_block; ++step) {
+      out[b * per_block + step] = cost_block_tile(b, blocks, rot, bands, per_block, step);
+    }
+  }
+  return blocks;
 }

@@ -50,6 +50,11 @@ namespace derp {
 #ifndef DERP_PHASE_TIMERS
 #define DERP_PHASE_TIMERS 0
 #endif
+// tools/block_trace.py: every random-proposal / ping-pong block records when it started and ended (s_memrealtime, the
+// 100 MHz clock all XCDs share) in LevelView::blockTrace
+#ifndef DERP_BLOCK_TRACE
+#define DERP_BLOCK_TRACE 0
+#endif
 // DERP_COUNT_UNION (tools/union_probe.py): counter slots [2] / [3] hold the SSD iterations the waves walk
 // DERP_COUNT_PP_FILL (tools/pp_fill_probe.py): ping-pong's counter slot [1] holds the lane-slots its waves walk
 static constexpr int kCostBlock = 64;  // threads per cost-kernel block: ONE wave (tile_pixel)
@@ -96,6 +101,9 @@ struct LevelView {
   const uint8_t* fovMask;     // [Dtotal][H*W]
   uint8_t* pairCount;            // [Dtotal][H*W] #pairs behind cost[] where random proposals evaluated the pixel
   unsigned long long* counters;  // [0] nCost [1] nPair [2] insufficient coverage [3] cost evaluations served from memo
+#if DERP_BLOCK_TRACE
+  unsigned long long* blockTrace;  // [gridDim.y][gridDim.x] {start, end} of the launch's blocks, or null
+#endif
 };
 
 __device__ __forceinline__ size_t warp_plane(const LevelView& V) {
@@ -131,10 +139,26 @@ __device__ __forceinline__ T& at32(T* base, unsigned i) {
 // `rot` rotates which band an XCD gets (callers pass the destination index): the top and bottom bands of
 // every image hold the clipped FOV-circle corners, i.e. less work, and without the rotation the same two
 // XCDs would draw them for every destination of the launch and idle at its end.
-__device__ __forceinline__ int xcd_swizzle(int b, int n, int rot) {
+// `bands` (K, a power of two that divides n / 8; the launcher pads n, cost_grid): an XCD owns K thin bands spread over
+// the image instead of one thick one. The range is cut into 8 * K equal runs; the XCD walks its K runs one after
+// another, its k-th being run k * 8 + ((xcd + rot) & 7), and a run in the order it always had. What a destination's
+// pixels cost is uneven over the image (the FOV circle, the random-proposal gate), so one thick band per XCD leaves the
+// XCDs unequal shares and the early finishers idle; K bands per XCD average over the image. A run is never thinner than
+// one row of kTileBlock squares, which the tiles an XCD has in flight span already: the L2 footprint stays what it was.
+// K = 1 is the map above.
+__host__ __device__ __forceinline__ int xcd_swizzle(int b, int n, int rot, int bands) {
   const int per = (n + 7) >> 3;
-  const int t = (((b & 7) + rot) & 7) * per + (b >> 3);
-  return t;
+  if (bands <= 1) {
+    return (((b & 7) + rot) & 7) * per + (b >> 3);
+  }
+  const int run = per / bands;  // items per run
+  const int j = b >> 3, k = j / run;
+  return (k * 8 + (((b & 7) + rot) & 7)) * run + (j - k * run);
+}
+// A cost block walks `perBlock` (N) consecutive tiles, step 0 .. N - 1: those of item `xcd_swizzle(b, ...)` of a grid of
+// n blocks. N = 4 is the four 8x8 quads of one 16x16 super-tile (tile_pixel).
+__host__ __device__ __forceinline__ int cost_block_tile(int b, int n, int rot, int bands, int perBlock, int step) {
+  return xcd_swizzle(b, n, rot, bands) * perBlock + step;
 }
 
 // Pixel handled by this thread. A wave owns an 8x8 pixel tile; four consecutive waves form a 16x16
@@ -261,6 +285,34 @@ __device__ __forceinline__ LdsPairs cost_wave_prologue(const LevelView& V, int d
 #endif
   __syncthreads();
   return pairs;
+}
+// The same in two parts, for the blocks that walk several tiles (random proposals, ping-pong): the block's part, done
+// once (the lane's pair slots, and the place of the two tables), ...
+__device__ __forceinline__ LdsPairs cost_block_prologue(PatchWin*& win) {
+  static_assert(kCostBlock == 64, "a wave leaves an empty tile on its own: the block must be that one wave");
+  extern __shared__ SsdPair ldsPairs[];
+  __shared__ PatchWin patchWin[kCostBlock / 64];
+  win = &patchWin[threadIdx.x >> 6];
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ double atanLut[kAtanLutDoubles];
+  return LdsPairs{ldsPairs + threadIdx.x, (int)blockDim.x, atanLut};
+#else
+  return LdsPairs{ldsPairs + threadIdx.x, (int)blockDim.x, nullptr};
+#endif
+}
+// ... and the tile's part, all 64 lanes taking part: the window of this tile, and the atan table if no earlier tile of
+// the block filled it (`lutReady`, wave-uniform). The first barrier lets the previous tile's reads of the window finish.
+__device__ __forceinline__ void cost_tile_prologue(const LevelView& V, int d, int x0, int y0, PatchWin* win, const LdsPairs& pairs,
+                                                   bool& lutReady) {
+  __syncthreads();
+  patch_window_fill(V, V.dst2src[d], x0, y0, win);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (!lutReady) {
+    atan_lut_fill(const_cast<double*>(pairs.atanLut));
+    lutReady = true;
+  }
+#endif
+  __syncthreads();
 }
 
 // The texels one computeSSD call reads, requested ahead of the arithmetic: the 4x4 block of projColor
@@ -720,6 +772,27 @@ __device__ __forceinline__ unsigned phase_clock() {
   return (unsigned)__builtin_amdgcn_s_memtime();
 #else
   return 0u;
+#endif
+}
+// developer build (-DDERP_BLOCK_TRACE=1): a cost block's start and end on the clock the XCDs share, for the host to lay
+// the launch out per XCD (block id & 7) — tools/block_trace.py
+__device__ __forceinline__ unsigned long long block_trace_begin() {
+#if DERP_BLOCK_TRACE
+  return (unsigned long long)wall_clock64();
+#else
+  return 0ull;
+#endif
+}
+__device__ __forceinline__ void block_trace_end(const LevelView& V, unsigned long long t0) {
+#if DERP_BLOCK_TRACE
+  if ((threadIdx.x & 63) == 0 && V.blockTrace) {
+    unsigned long long* e = V.blockTrace + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+    e[0] = t0;
+    e[1] = (unsigned long long)wall_clock64();
+  }
+#else
+  (void)V;
+  (void)t0;
 #endif
 }
 // The LEAN variant of `sees` (derp_camera.h) the cost kernels project through (bit 1: the short fp64 atan2 / division
@@ -1587,83 +1660,74 @@ __global__ void __launch_bounds__(256) k_row_rank(LevelView V, int* __restrict__
   }
 }
 
-// (the body of k_random_proposals / k_random_proposals_w3: the same code under two register budgets, see below)
-__device__ __forceinline__ void random_proposals_body(const LevelView& V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
-  const int dl = blockIdx.y;
+// One tile of random proposals: the lanes whose pixel passed the gate (`go`) evaluate its current disparity and the
+// proposals; every lane of the wave takes part in the counters' reduction.
+__device__ __forceinline__ void random_proposals_tile(const LevelView& V, const int* __restrict__ rank, int dl, int x, int y, bool go,
+                                                      const PatchWin* win, LdsPairs& pairs) {
   const int d = V.dst0 + dl;
-  int x, y;
-  tile_pixel(xcd_swizzle(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0), tilesX, x, y);
-  PatchWin* win;
-  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
+  const int own = V.dst2src[d];
+  // per-destination planes (wave-uniform bases) and a 32-bit pixel index, as in k_ping_pong
+  const size_t n = (size_t)V.W * V.H;
+  const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
+  float* disp = V.disparity + (size_t)d * n;
   unsigned nCost = 0, nPair = 0, nSlots = 0, nSlotsFirst = 0;
   PhaseTimers tm;
   const unsigned tk0 = phase_clock();
-  if (x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1) {
-    const int own = V.dst2src[d];
-    // per-destination planes (wave-uniform bases) and a 32-bit pixel index, as in k_ping_pong
-    const size_t n = (size_t)V.W * V.H;
-    const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
-    float* disp = V.disparity + (size_t)d * n;
-    if ((V.fovMask + (size_t)d * n)[idx]) {
-      if (!(V.srcFg + (size_t)own * n)[idx]) {
-        disp[idx] = (V.bgDisp + (size_t)d * n)[idx];
-      } else if (random_gate(V, d, own, idx)) {
-        PixCtx px;
-        load_pixctx<false>(V, d, own, x, y, win, px);
-        const unsigned cull = behind_sources(V, d, idx);
-        // What the proposal loop carries per lane: the pixel index, the current disparity / cost / confidence / pair count,
-        // the acceptance threshold, the amplitude, the engine state, the pair counter; the lower bound of the range is
-        // read again per proposal.
-        // One copy of computeCost serves the evaluation of the current disparity (i = -1) and the proposals: the kernel's
-        // code is half the size it was with two inlined copies (45 KB against a 64 KB instruction cache).
-        float currDisp = at32(disp, idx);
-        float currCost = 0.f, costThresh = 0.f, amplitude = 0.f;
-        // the confidence and pair count of the current best ride in the lane's spare pair slot (S slots are allocated, S - 1
-        // sources use them): results, read back once after the loop
-        const int spare = V.S - 1;
-        const float maxDisp = 1.0f / V.minDepthM;
-        uint32_t state = (uint32_t)at32(rank + (size_t)d * n, idx);  // minstd_rand0 positioned by k_row_rank
-        for (int i = -1; i < V.randomProposals; ++i) {
-          unsigned pi = idx;
-          asm("" : "+v"(pi) : "s"(i));  // (opaque per proposal: the loads below stay inside the loop)
-          const float minDisp = V.hasFg ? at32(V.bgDisp + (size_t)d * n, pi) : (1.0f / V.maxDepthM);
-          float propDisp = currDisp;
-          if (i >= 0) {
-            const float lo = fmaxf(minDisp, currDisp - amplitude), hi = fminf(maxDisp, currDisp + amplitude);
-            propDisp = minstd_uniform(state, lo, hi);
-          }
-          unsigned np = 0;
-          const float2 pr = compute_cost<true, true>(V, dl, own, px, propDisp, pairs, np, cull, pi, i < 0 ? &nSlotsFirst : &nSlots, &tm);
-          nPair += np;
-          bool take;
-          if (i < 0) {
-            costThresh = fminf(0.5f * pr.x, 5.0f);  // kRandomPropMaxCost
-            amplitude = (maxDisp - minDisp) / 2.0f;
-            take = true;
-          } else {
-            take = pr.x < currCost && pr.x < costThresh;
-            if (take) {
-              amplitude /= 2.0f;
-            }
-          }
-          if (take) {
-            currCost = pr.x;
-            currDisp = propDisp;
-            pairs.set(spare, SsdPair{pr.y, __uint_as_float(np)});
-          }
+  if (go) {
+    PixCtx px;
+    load_pixctx<false>(V, d, own, x, y, win, px);
+    const unsigned cull = behind_sources(V, d, idx);
+    // What the proposal loop carries per lane: the pixel index, the current disparity / cost / confidence / pair count,
+    // the acceptance threshold, the amplitude, the engine state, the pair counter; the lower bound of the range is
+    // read again per proposal.
+    // One copy of computeCost serves the evaluation of the current disparity (i = -1) and the proposals: the kernel's
+    // code is half the size it was with two inlined copies (45 KB against a 64 KB instruction cache).
+    float currDisp = at32(disp, idx);
+    float currCost = 0.f, costThresh = 0.f, amplitude = 0.f;
+    // the confidence and pair count of the current best ride in the lane's spare pair slot (S slots are allocated, S - 1
+    // sources use them): results, read back once after the loop
+    const int spare = V.S - 1;
+    const float maxDisp = 1.0f / V.minDepthM;
+    uint32_t state = (uint32_t)at32(rank + (size_t)d * n, idx);  // minstd_rand0 positioned by k_row_rank
+    for (int i = -1; i < V.randomProposals; ++i) {
+      unsigned pi = idx;
+      asm("" : "+v"(pi) : "s"(i));  // (opaque per proposal: the loads below stay inside the loop)
+      const float minDisp = V.hasFg ? at32(V.bgDisp + (size_t)d * n, pi) : (1.0f / V.maxDepthM);
+      float propDisp = currDisp;
+      if (i >= 0) {
+        const float lo = fmaxf(minDisp, currDisp - amplitude), hi = fminf(maxDisp, currDisp + amplitude);
+        propDisp = minstd_uniform(state, lo, hi);
+      }
+      unsigned np = 0;
+      const float2 pr = compute_cost<true, true>(V, dl, own, px, propDisp, pairs, np, cull, pi, i < 0 ? &nSlotsFirst : &nSlots, &tm);
+      nPair += np;
+      bool take;
+      if (i < 0) {
+        costThresh = fminf(0.5f * pr.x, 5.0f);  // kRandomPropMaxCost
+        amplitude = (maxDisp - minDisp) / 2.0f;
+        take = true;
+      } else {
+        take = pr.x < currCost && pr.x < costThresh;
+        if (take) {
+          amplitude /= 2.0f;
         }
-        {
-          unsigned pi = idx;
-          asm("" : "+v"(pi) : "v"(currCost));
-          const SsdPair best = pairs.get(spare);
-          at32(V.confidence + (size_t)d * n, pi) = best.first;
-          at32(V.pairCount + (size_t)d * n, pi) = (uint8_t)__float_as_uint(best.second);
-          at32(disp, pi) = currDisp;
-          at32(V.cost + (size_t)d * n, pi) = currCost;
-        }
-        nCost = 1u + (unsigned)max(V.randomProposals, 0);
+      }
+      if (take) {
+        currCost = pr.x;
+        currDisp = propDisp;
+        pairs.set(spare, SsdPair{pr.y, __uint_as_float(np)});
       }
     }
+    {
+      unsigned pi = idx;
+      asm("" : "+v"(pi) : "v"(currCost));
+      const SsdPair best = pairs.get(spare);
+      at32(V.confidence + (size_t)d * n, pi) = best.first;
+      at32(V.pairCount + (size_t)d * n, pi) = (uint8_t)__float_as_uint(best.second);
+      at32(disp, pi) = currDisp;
+      at32(V.cost + (size_t)d * n, pi) = currCost;
+    }
+    nCost = 1u + (unsigned)max(V.randomProposals, 0);
   }
 #if DERP_PHASE_TIMERS
   if ((threadIdx.x & 63) == 0) {
@@ -1681,18 +1745,68 @@ __device__ __forceinline__ void random_proposals_body(const LevelView& V, const 
 #endif
 }
 
+// (the body of k_random_proposals / k_random_proposals_w3: the same code under two register budgets, see below)
+// A block (one wave) walks `perBlock` consecutive tiles (cost_block_tile); what it carries from tile to tile is scalar:
+// the step, and whether the atan table is filled. A tile none of whose pixels passes the gate is left before the wave
+// pays for its window and the table: the gate and the background write need neither, and such a tile counts nothing.
+// WALK = false is the block of one tile without the loop: around the loop the compiler keeps the level's scalars live from
+// tile to tile, which costs the walking kernels scalar and then vector spills (profiles/r13_kernel_resources.txt).
+template <bool WALK>
+__device__ __forceinline__ void random_proposals_body(const LevelView& V, const int* __restrict__ rank, int tilesX, int bands,
+                                                      int perBlock) {
+  const unsigned long long bt0 = block_trace_begin();
+  const int steps = WALK ? perBlock : 1;
+  const int dl = blockIdx.y;
+  const int d = V.dst0 + dl;
+  PatchWin* win;
+  LdsPairs pairs = cost_block_prologue(win);
+  bool lutReady = false;
+  for (int step = 0; step < steps; ++step) {
+    int x, y;
+    tile_pixel(cost_block_tile(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0, bands, steps, step), tilesX, x, y);
+    bool go = false;
+    if (x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1) {
+      const int own = V.dst2src[d];
+      const size_t n = (size_t)V.W * V.H;
+      const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
+      if ((V.fovMask + (size_t)d * n)[idx]) {
+        if (!(V.srcFg + (size_t)own * n)[idx]) {
+          (V.disparity + (size_t)d * n)[idx] = (V.bgDisp + (size_t)d * n)[idx];
+        } else {
+          go = random_gate(V, d, own, idx);
+        }
+      }
+    }
+    if (__ballot(go) == 0ull) {
+      continue;
+    }
+    cost_tile_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win, pairs, lutReady);
+    random_proposals_tile(V, rank, dl, x, y, go, win, pairs);
+  }
+  block_trace_end(V, bt0);
+}
+
 // Two register budgets for the same body. Up to 16 cameras a wave's LDS (8 B x 64 lanes x S pair slots + the patch window)
 // lets sixteen one-wave blocks share a CU: the kernels are held to 128 VGPRs = FOUR waves per SIMD. With more cameras the
 // pair slots fill the LDS first (24 cameras: twelve blocks = three waves) and the 128-register build would pay its spills
 // and tighter schedule for nothing: the _w3 kernels keep the 168 registers of three waves (config 4, same box: 261 -> 271
 // Mpix/s, profiles/r06_kernel_variants.txt run 9). The launcher picks by camera count (cost_four_waves, derp_capi.hip).
 __global__ void __launch_bounds__(kCostBlock, DERP_RANDOM_MIN_WAVES)
-    k_random_proposals(LevelView V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
-  random_proposals_body(V, rank, tilesX, tilesPerDst);
+    k_random_proposals(LevelView V, const int* __restrict__ rank, int tilesX, int bands, int perBlock) {
+  random_proposals_body<false>(V, rank, tilesX, bands, perBlock);
 }
 __global__ void __launch_bounds__(kCostBlock, 3)
-    k_random_proposals_w3(LevelView V, const int* __restrict__ rank, int tilesX, int tilesPerDst) {
-  random_proposals_body(V, rank, tilesX, tilesPerDst);
+    k_random_proposals_w3(LevelView V, const int* __restrict__ rank, int tilesX, int bands, int perBlock) {
+  random_proposals_body<false>(V, rank, tilesX, bands, perBlock);
+}
+// ... and the same two with blocks that walk perBlock > 1 tiles (cost_grid, derp_capi.hip)
+__global__ void __launch_bounds__(kCostBlock, DERP_RANDOM_MIN_WAVES)
+    k_random_proposals_walk(LevelView V, const int* __restrict__ rank, int tilesX, int bands, int perBlock) {
+  random_proposals_body<true>(V, rank, tilesX, bands, perBlock);
+}
+__global__ void __launch_bounds__(kCostBlock, 3)
+    k_random_proposals_walk_w3(LevelView V, const int* __restrict__ rank, int tilesX, int bands, int perBlock) {
+  random_proposals_body<true>(V, rank, tilesX, bands, perBlock);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1849,6 +1963,11 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
       }
     }
   }
+  // a tile without a task (no pixel evaluates, or every candidate was rejected or memoised) is finished: no cull ballots,
+  // no prefix sum, no batch (x and y are what they were)
+  if (__ballot(cmask != 0u) == 0ull) {
+    return;
+  }
   // the cull mask of the evaluating lanes (behind_sources' ballot, with the other lanes made neutral)
   unsigned cull = 0;
   const unsigned behind = eval ? V.behind[(size_t)d * n + idx] : ~0u;
@@ -1934,15 +2053,12 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
   y = y0 + (lane >> 3);
 }
 
+// One tile of a ping-pong iteration; every lane of the wave takes part.
 template <bool COMPACT>
-__device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                                               float* __restrict__ costRes, int tilesX, int useMemo) {
-  const int dl = blockIdx.y;
+__device__ __forceinline__ void ping_pong_tile(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
+                                               float* __restrict__ costRes, int dl, int x, int y, const PatchWin* win, LdsPairs& pairs,
+                                               int useMemo) {
   const int d = V.dst0 + dl;
-  int x, y;
-  tile_pixel(xcd_swizzle(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0), tilesX, x, y);
-  PatchWin* win;
-  LdsPairs pairs = cost_wave_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win);
   // per-lane counters in one register: pairs (bits 0..15: <= 10 * 31), cost evaluations (16..23: <= 10), memoised (24..)
   unsigned counts = 0, fillSlots = 0;
   PhaseTimers tm;
@@ -1985,28 +2101,45 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
   }
 }
 
+// The block walks `perBlock` consecutive tiles like random proposals' (random_proposals_body): the atan table once, the
+// window per tile, nothing per lane carried from one tile to the next.
+template <bool COMPACT, bool WALK>
+__device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
+                                               float* __restrict__ costRes, int tilesX, int useMemo, int bands, int perBlock) {
+  const unsigned long long bt0 = block_trace_begin();
+  const int steps = WALK ? perBlock : 1;
+  const int dl = blockIdx.y;
+  const int d = V.dst0 + dl;
+  PatchWin* win;
+  LdsPairs pairs = cost_block_prologue(win);
+  bool lutReady = false;
+  for (int step = 0; step < steps; ++step) {
+    int x, y;
+    tile_pixel(cost_block_tile(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0, bands, steps, step), tilesX, x, y);
+    cost_tile_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win, pairs, lutReady);
+    ping_pong_tile<COMPACT>(V, changed, dispRes, costRes, dl, x, y, win, pairs, useMemo);
+  }
+  block_trace_end(V, bt0);
+}
+
 // Two register budgets (see k_random_proposals_w3) x two candidate loops: the compacted one, and the one-pixel-per-lane
 // loop it replaced (DERP_PP_COMPACT=0, developer A/B). The launcher picks (run_ping_pong, derp_capi.hip).
-__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
-    k_ping_pong(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
-}
-__global__ void __launch_bounds__(kCostBlock, 3)  // more than 16 cameras: see k_random_proposals_w3
-    k_ping_pong_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                   float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body<true>(V, changed, dispRes, costRes, tilesX, useMemo);
-}
-__global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
-    k_ping_pong_loop(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                     float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
-}
-__global__ void __launch_bounds__(kCostBlock, 3)
-    k_ping_pong_loop_w3(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                        float* __restrict__ costRes, int tilesX, int useMemo) {
-  ping_pong_body<false>(V, changed, dispRes, costRes, tilesX, useMemo);
-}
+#define DERP_PING_PONG_KERNEL(NAME, WAVES, COMPACT, WALK)                                                                   \
+  __global__ void __launch_bounds__(kCostBlock, WAVES)                                                                      \
+      NAME(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes, float* __restrict__ costRes,     \
+           int tilesX, int useMemo, int bands, int perBlock) {                                                              \
+    ping_pong_body<COMPACT, WALK>(V, changed, dispRes, costRes, tilesX, useMemo, bands, perBlock);                          \
+  }
+DERP_PING_PONG_KERNEL(k_ping_pong, DERP_COST_MIN_WAVES, true, false)
+DERP_PING_PONG_KERNEL(k_ping_pong_w3, 3, true, false)  // more than 16 cameras: see k_random_proposals_w3
+DERP_PING_PONG_KERNEL(k_ping_pong_loop, DERP_COST_MIN_WAVES, false, false)
+DERP_PING_PONG_KERNEL(k_ping_pong_loop_w3, 3, false, false)
+// ... and the same four with blocks that walk perBlock > 1 tiles
+DERP_PING_PONG_KERNEL(k_ping_pong_walk, DERP_COST_MIN_WAVES, true, true)
+DERP_PING_PONG_KERNEL(k_ping_pong_walk_w3, 3, true, true)
+DERP_PING_PONG_KERNEL(k_ping_pong_loop_walk, DERP_COST_MIN_WAVES, false, true)
+DERP_PING_PONG_KERNEL(k_ping_pong_loop_walk_w3, 3, false, true)
+#undef DERP_PING_PONG_KERNEL
 
 // changed = disp != dispRes; dispRes -> disp; costRes -> cost (Derp.cpp:527-529)
 __global__ void k_ping_pong_commit(float* __restrict__ disp, float* __restrict__ cost, const float* __restrict__ dispRes,

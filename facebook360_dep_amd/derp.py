@@ -103,7 +103,7 @@ EXPORTS = [
     "derp_level_begin", "derp_stage_reproject_colors", "derp_stage_brute_force", "derp_stage_random_proposals",
     "derp_stage_ping_pong", "derp_stage_mismatches", "derp_stage_bilateral_filter", "derp_stage_median_filter", "derp_stage_mask_fov",
     "derp_level_end", "derp_set_level_disparity", "derp_get_level_disparity", "derp_cost_map", "derp_debug_download",
-    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees",
+    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees", "derp_debug_block_trace",
     "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
     "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
     "derp_render_vertices",
@@ -114,7 +114,7 @@ EXPORTS = [
     "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
     "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
     "derp_get_counters", "derp_reset_counters", "derp_profile_enable", "derp_profile_reset", "derp_profile_query", "derp_profile_memoised",
-    "derp_device_name", "derp_device_memory", "derp_host_nth_element_pairs", "derp_host_minstd_uniform",
+    "derp_device_name", "derp_device_memory", "derp_host_nth_element_pairs", "derp_host_minstd_uniform", "derp_host_cost_tile_map",
     "derp_set_frame_slots", "derp_select_frame", "derp_frame_slots", "derp_host_alloc", "derp_host_free", "derp_bind_thread", "derp_host_register", "derp_host_unregister",
     "derp_seq_options_default", "derp_seq_window", "derp_seq_owner", "derp_seq_plan", "derp_seq_create", "derp_seq_destroy",
     "derp_seq_counts", "derp_seq_frames", "derp_seq_frame_slot", "derp_seq_buffer", "derp_rccl_unique_id",
@@ -748,6 +748,15 @@ class Derp:
         self._ck(lib().derp_profile_memoised(self.h, stage.encode(), level, C.byref(m)))
         return m.value
 
+    def block_trace(self, stage, level):
+        """-> uint64 [grid_y, grid_x, 2]: start / end (10 ns ticks) of the blocks of the stage's last launch at `level`
+        (a library built with -DDERP_BLOCK_TRACE=1 only)"""
+        gx, gy = C.c_int(), C.c_int()
+        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, None, C.c_size_t(0), C.byref(gx), C.byref(gy)))
+        out = np.zeros((gy.value, gx.value, 2), dtype=np.uint64)
+        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, _p(out), C.c_size_t(out.size), C.byref(gx), C.byref(gy)))
+        return out
+
     def device_memory(self):
         """-> (free, total) bytes of HBM right now"""
         f, t = C.c_uint64(), C.c_uint64()
@@ -799,6 +808,16 @@ def host_nth_element_pairs(pairs, nth):
 
 def host_minstd_uniform(seed, draw_index, a, b):
     return lib().derp_host_minstd_uniform(seed, draw_index, C.c_float(a), C.c_float(b))
+
+
+def host_cost_tile_map(tiles, bands, rot, per_block):
+    """Tile order of a random-proposal / ping-pong launch: int32 array [blocks, per_block] (host arithmetic, no GPU)."""
+    cap = (tiles + 8 * bands * per_block) // per_block * per_block + 8 * bands * per_block
+    out = np.empty(cap, dtype=np.int32)
+    blocks = lib().derp_host_cost_tile_map(tiles, bands, rot, per_block, _p(out), cap)
+    if blocks <= 0:
+        raise ValueError("bad tile map arguments")
+    return out[:blocks * per_block].reshape(blocks, per_block)
 
 
 def average_score(score, mask):

@@ -200,6 +200,11 @@ int derp_debug_fp64(derp_ctx* ctx, int op, const double* a, const double* b, dou
  * for the rig points xyz[3 i .. 3 i + 2]; pix is NaN where the point lies outside the FOV cone */
 int derp_debug_sees(derp_ctx* ctx, int src, const double* xyz, size_t n, double* out);
 
+/* developer builds (-DDERP_BLOCK_TRACE=1, tools/block_trace.py): {start, end} in 10 ns ticks of every block of the last
+ * random-proposal ("random_proposals") / ping-pong ("ping_pong") launch of `level`, out[(y * grid_x + x) * 2 ..]; with
+ * out = NULL or too small a capacity (in uint64s) only the grid is returned. Fails in the shipped library. */
+int derp_debug_block_trace(derp_ctx* ctx, const char* stage, int level, uint64_t* out, size_t capacity, int* grid_x, int* grid_y);
+
 /* mismatch mask of the level processed last (dstMismatchedDisparityMask, PyramidLevel.h:332-338) */
 int derp_download_mismatch_mask(derp_ctx* ctx, int dst, uint8_t* out);
 
@@ -673,6 +678,11 @@ int derp_device_memory(derp_ctx* ctx, uint64_t* free_bytes, uint64_t* total_byte
 /* host-only self checks (no GPU needed): restated libstdc++ algorithms the device code uses */
 int derp_host_nth_element_pairs(float* pairs, int n, int nth);
 float derp_host_minstd_uniform(int seed, uint64_t draw_index, float a, float b);
+/* the tile order of the random-proposal / ping-pong launches: out[b * per_block + step] = the tile that block b of the
+ * grid handles at `step` of its walk, for a level of `tiles` tiles, `bands` bands per XCD (1, 2, 4), band rotation `rot`
+ * (the destination index) and `per_block` tiles per block (1, 2, 4). Returns the number of blocks of the grid (a tile
+ * index at or past `tiles` is padding), or 0 on bad arguments or when `capacity` ints do not hold the map. */
+int derp_host_cost_tile_map(int tiles, int bands, int rot, int per_block, int* out, int capacity);
 
 #ifdef __cplusplus
 }
