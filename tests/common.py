@@ -90,6 +90,37 @@ def mixed_type_rig(res):
     return {"cameras": cams}
 
 
+def real_rig(n=6, drop_principal=()):
+    """The first `n` cameras of the reference's own test rig (tests/golden/ref_test_rig.json: real calibration,
+    3360 x 2160, off-centre principal points, rotations that need re-unitarising). Cameras whose index is in
+    `drop_principal` lose their "principal" key: the file's default, resolution / 2 (Camera.cpp:44-48)."""
+    import json
+
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_test_rig.json")
+    with open(path) as f:
+        cams = [dict(c) for c in json.load(f)["cameras"][:n]]
+    for i in drop_principal:
+        del cams[i]["principal"]
+    return {"cameras": cams}
+
+
+def real_rig_no_principal(n=6):
+    """real_rig with cameras 1 and 4 left without a principal point"""
+    return real_rig(n, drop_principal=(1, 4))
+
+
+def perturbed_disparities(truth):
+    """test_canopy_cubemap's perturbation of a frame's true disparities (four cameras or more), scaled to the image:
+    a foreground slab (long stretched triangles at its border), a NaN hole and 2 % noise."""
+    disps = [np.asarray(d, dtype=np.float32).copy() for d in truth]
+    h, w = disps[0].shape
+    rng = np.random.default_rng(3)
+    disps[1][h // 5:2 * h // 5, w // 3:w // 2] *= 2.5
+    disps[3][5 * h // 8:5 * h // 8 + 4, w // 10:w // 10 + 4] = np.nan
+    disps[-1] = disps[-1] * (1 + 0.02 * rng.standard_normal(disps[-1].shape)).astype(np.float32)
+    return disps
+
+
 def compare_disparity(got, ref, tol=1e-4):
     """-> (#pixels off by more than `tol` relative or with mismatching NaN-ness, max relative error
     over the pixels that are finite in both)."""

@@ -1,17 +1,20 @@
 """numpy restatements of the reference's conversion loops for tests/test_gpu_conversion*.py, on top of the oracle's
 camera (oracle_lib.Rig built from the un-normalised cameras, Camera::rescale'd like the tools do), and the inputs
 those tests share. Nothing here touches the GPU."""
+import json
+
 import numpy as np
 
 F32, F64 = np.float32, np.float64
 
 
-def rescaled_rig(cams, w, h):
+def rescaled_rig(cams, w, h=None):
+    """every camera rescaled to w x h, or camera i to w[i] when `w` is a list of sizes"""
     from oracle import oracle_lib as O
 
     rig = O.Rig(cams)
     for i in range(len(cams)):
-        rig.rescale(i, w, h)
+        rig.rescale(i, *((w, h) if h is not None else w[i]))
     return rig
 
 
@@ -38,18 +41,37 @@ def export_inputs(cam, w, h):
     return disp, bgr.astype(F32) / F32(65535)
 
 
-_outside = {}  # (camera id, w, h) -> isOutsideImageCircle of every pixel centre, computed once
+_outside = {}  # (the whole camera description, w, h) -> isOutsideImageCircle of every pixel centre, computed once
 
 
 def outside_image_circle(rig, cams, cam, w, h):
-    key = (cams[cam]["id"], w, h)
+    # (the id alone does not do: every rig of the tests calls its cameras cam0, cam1, ...)
+    key = (json.dumps(cams[cam], sort_keys=True), w, h)
     if key not in _outside:
         _outside[key] = np.array([rig.is_outside_image_circle(cam, px, py) for px, py in pixel_centres(w, h)])
     return _outside[key]
 
 
-def export_points(cams, cam, disp, color, max_depth, clip):
-    """-> (f32 [count, 6] x y z r g b in row-major pixel order, pixels outside the image circle)"""
+def mix32(h):
+    """derp_points.h's mix32 (the murmur3 finaliser) on uint32 arrays, which wrap like the device's uint32_t"""
+    h = np.asarray(h, dtype=np.uint32).copy()
+    h ^= h >> np.uint32(16)
+    h *= np.uint32(0x85EBCA6B)
+    h ^= h >> np.uint32(13)
+    h *= np.uint32(0xC2B2AE35)
+    h ^= h >> np.uint32(16)
+    return h
+
+
+def subsample_keeps(cam_index, pixels, subsample):
+    """derp_points.h's subsample_keeps: which pixel indices --subsample=N keeps for camera `cam_index`"""
+    seed = mix32(np.array([(cam_index + 0x9E3779B9) & 0xFFFFFFFF], dtype=np.uint32))
+    return mix32(np.asarray(pixels, dtype=np.uint32) ^ seed) % np.uint32(subsample) == 0
+
+
+def export_points(cams, cam, disp, color, max_depth, clip, cam_index=None, subsample=1):
+    """-> (f32 [count, 6] x y z r g b in row-major pixel order, pixels outside the image circle). `subsample` > 1
+    keeps the pixels subsample_keeps names for `cam_index` (the camera's own index unless given)."""
     h, w = disp.shape
     rig = rescaled_rig(cams, w, h)
     pix = pixel_centres(w, h)
@@ -60,6 +82,8 @@ def export_points(cams, cam, disp, color, max_depth, clip):
         depth = norm3(world)
         over = depth > max_depth
         keep = ~outside
+        if subsample > 1:
+            keep &= subsample_keeps(cam if cam_index is None else cam_index, np.arange(w * h), subsample)
         if clip:
             keep &= ~over
         else:
@@ -80,16 +104,85 @@ def random_cloud(n, seed):
     return np.ascontiguousarray(np.concatenate([pts[: n // 2], extra, pts[n // 2:]]))
 
 
-def import_points(cams, pts, w, h, min_depth, max_depth):
-    rig = rescaled_rig(cams, w, h)
+EDGE_POINTS = 12  # clamp_cloud's points per camera and axis
+
+
+def clamp_cloud(cams, sizes, depth=2.0):
+    """Points that camera i projects a quarter pixel inside its right edge (x = w - 0.25) and its bottom edge
+    (y = h - 0.25): std::round puts them on w (h), the clamp back on w - 1 (h - 1) (ImportPointCloud.cpp:108-109).
+    Made with the reference's own unprojection, EDGE_POINTS per camera and axis, spread about the principal point
+    along the edge, `depth` metres along the ray. -> (f64 [n, 3], camera of each point, axis of each point: 0 = x)"""
+    rig = rescaled_rig(cams, sizes)
+    pts, owner, axis = [], [], []
+    t = np.linspace(-0.1, 0.1, EDGE_POINTS)  # (the mixed rig's FTHETA circle crosses the edge 0.148 either side)
+    for i, (w, h) in enumerate(sizes):
+        pr = rig.state(i)["principal"]
+        ys = np.clip(pr[1] + t * h, 0.05, h - 0.05)
+        xs = np.clip(pr[0] + t * w, 0.05, w - 0.05)
+        pix = np.concatenate([np.stack([np.full(EDGE_POINTS, w - 0.25), ys], axis=1),
+                              np.stack([xs, np.full(EDGE_POINTS, h - 0.25)], axis=1)])
+        pts.append(rig.rig(i, pix, depth))
+        owner += [i] * (2 * EDGE_POINTS)
+        axis += [0] * EDGE_POINTS + [1] * EDGE_POINTS
+    return np.ascontiguousarray(np.concatenate(pts)), np.array(owner), np.array(axis)
+
+
+def boundary_depths(min_depth, max_depth):
+    """the float values at and one ulp either side of both limits -> [(float32 depth, kept by the import)]"""
+    out = []
+    for limit in (F32(min_depth), F32(max_depth)):
+        assert float(limit) in (min_depth, max_depth)  # the limits are floats: `==` after the rounding can happen
+        for f in (np.nextafter(limit, F32(0)), limit, np.nextafter(limit, F32(np.inf))):
+            out.append((f, min_depth <= float(f) <= max_depth))
+    return out
+
+
+def boundary_cloud(cams, min_depth, max_depth):
+    """Points whose distance from the rig origin, ROUNDED TO FLOAT (ImportPointCloud.cpp:110), is each of
+    boundary_depths: for every such float three points, of fp64 norm the float itself and 2^-27 (relative) either
+    side of it, which all round to it. The 18 points look out of the rig along camera 0's and camera 1's forward
+    axis, tilted on a grid of 0.08 rad so that each has a pixel of its own in an image of 40 pixels or more across.
+    -> (f64 [36, 3], float32 depth of each point, kept flag of each point)"""
+    pts, depths, kept = [], [], []
+    for ci in (0, 1):
+        fwd, right, up = (np.array(cams[ci][k], dtype=F64) for k in ("forward", "right", "up"))
+        k = 0
+        for f, keep in boundary_depths(min_depth, max_depth):
+            for rel in (0.0, -(2.0 ** -27), 2.0 ** -27):
+                d = fwd + 0.08 * (k % 6 - 2.5) * right + 0.08 * (k // 6 - 1) * up
+                k += 1
+                p = d * (float(f) * (1 + rel) / norm3(d[None])[0])
+                assert F32(norm3(p[None])[0]) == f and (rel == 0.0 or norm3(p[None])[0] != float(f))
+                pts.append(p)
+                depths.append(f)
+                kept.append(keep)
+    return np.ascontiguousarray(np.array(pts)), np.array(depths, dtype=F32), np.array(kept)
+
+
+def special_rows():
+    """rows with an infinite coordinate of either sign, and the zero vector: none may touch an image"""
+    inf = np.inf
+    return np.array([[inf, 1.0, 0.2], [-inf, 0.5, 0.5], [1.0, -inf, 0.3], [0.2, 0.1, inf], [inf, -inf, inf],
+                     [0.0, 0.0, 0.0]])
+
+
+def import_points(cams, pts, sizes, min_depth, max_depth):
+    """sizes: one (w, h) per camera -> one f32 [h, w] disparity image per camera"""
+    rig = rescaled_rig(cams, sizes)
+    pts = np.ascontiguousarray(pts, dtype=F64).reshape(-1, 3)
     with np.errstate(all="ignore"):
         depth = norm3(pts).astype(F32)  # from the rig origin (reference quirk)
         depth[(depth.astype(F64) < min_depth) | (depth.astype(F64) > max_depth)] = np.inf
         cand = F32(1.0) / depth
+        # `std::max(disparity(ySrc, xSrc), 1.0f / depth)` (:114-115) on an image that starts at 0 (:83): std::max(old, NaN)
+        # == old, and std::max(old, 0) == old since no pixel goes below 0. Only positive candidates are looked at; a
+        # point with an infinite coordinate has none (its depth is set to INFINITY, :111-112), and no pixel either
+        live = cand > 0
     images = []
-    for i in range(len(cams)):
+    pts, cand = pts[live], cand[live]
+    for i, (w, h) in enumerate(sizes):
         seen, pix = rig.sees(i, pts)
-        sel = seen & ~np.isnan(cand)  # std::max(old, NaN) == old
+        sel = seen
         xs = np.clip(np.floor(pix[sel, 0] + 0.5).astype(np.int64), 0, w - 1)  # std::round of a non-negative value
         ys = np.clip(np.floor(pix[sel, 1] + 0.5).astype(np.int64), 0, h - 1)
         img = np.zeros((h, w), F32)

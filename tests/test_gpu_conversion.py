@@ -64,23 +64,29 @@ def test_export_bit_for_bit(ctx, export_inputs, size, cam, max_depth, clip):
 
 def test_export_subsample(ctx, export_inputs):
     cams, g = ctx
-    disp, color = export_inputs[(50, 38, 0)]
-    full = g.export_points(0, disp, color)
-    a = g.export_points(0, disp, color, subsample=4)
-    b = g.export_points(0, disp, color, subsample=4)
-    assert a.tobytes() == b.tobytes()
-    rows = [r.tobytes() for r in full]
-    at = 0
-    for r in a:  # an in-order subset of the subsample=1 output
-        r = r.tobytes()
-        while at < len(rows) and rows[at] != r:
+    for cam in (0, 2):
+        disp, color = export_inputs[(50, 38, cam)]
+        full = g.export_points(cam, disp, color)
+        a = g.export_points(cam, disp, color, subsample=4)
+        b = g.export_points(cam, disp, color, subsample=4)
+        assert a.tobytes() == b.tobytes()
+        # exactly the rows that the hash of (camera index, pixel index) names, of the reference's output
+        want, _ = ref.export_points(cams, cam, disp, color, math.inf, False, subsample=4)
+        assert a.shape == want.shape and np.array_equal(a, want, equal_nan=True)
+        other, _ = ref.export_points(cams, cam, disp, color, math.inf, False, cam_index=cam + 1, subsample=4)
+        assert other.shape != want.shape or not np.array_equal(other, want, equal_nan=True)  # the camera index counts
+        rows = [r.tobytes() for r in full]
+        at = 0
+        for r in a:  # an in-order subset of the subsample=1 output
+            r = r.tobytes()
+            while at < len(rows) and rows[at] != r:
+                at += 1
+            assert at < len(rows), "a subsampled point is not in the full output, or out of order"
             at += 1
-        assert at < len(rows), "a subsampled point is not in the full output, or out of order"
-        at += 1
-    n = len(full)
-    sigma = math.sqrt(n * 0.25 * 0.75)
-    print("subsample=4: kept %d of %d (expected %.1f, sigma %.1f)" % (len(a), n, n / 4, sigma))
-    assert abs(len(a) - n / 4) <= 5 * sigma
+        n = len(full)
+        sigma = math.sqrt(n * 0.25 * 0.75)
+        print("subsample=4 cam %d: kept %d of %d (expected %.1f, sigma %.1f)" % (cam, len(a), n, n / 4, sigma))
+        assert abs(len(a) - n / 4) <= 5 * sigma
 
 
 # ---------------------------------------------------------------- import
@@ -101,7 +107,7 @@ def splat(g, n_cams, chunks):
 
 def test_import_bit_for_bit(ctx, cloud):
     cams, g = ctx
-    want = ref.import_points(cams, cloud, 32, 32, MIN_DEPTH, MAX_DEPTH)
+    want = ref.import_points(cams, cloud, [(32, 32)] * 4, MIN_DEPTH, MAX_DEPTH)
     one = splat(g, 4, [cloud])
     parts = splat(g, 4, [cloud[:7], cloud[7:71], cloud[71:]])
     hits = 0
@@ -122,7 +128,7 @@ def test_import_one_camera(built, cloud):
 
     cams = synth.make_rig(4, 64)["cameras"][1:2]
     g = derp.Derp(cams)
-    want = ref.import_points(cams, cloud, 32, 32, MIN_DEPTH, MAX_DEPTH)
+    want = ref.import_points(cams, cloud, [(32, 32)], MIN_DEPTH, MAX_DEPTH)
     got = splat(g, 1, [cloud[:64], cloud[64:]])
     g.close()
     assert got[0].tobytes() == want[0].tobytes() and (want[0] > 0).sum() > 100
