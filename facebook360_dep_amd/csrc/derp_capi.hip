@@ -115,7 +115,7 @@ LevelView make_view(derp_ctx* c, int stage, int dst0, int nd) {
   V.cost = c->w.cost.as<float>();
   V.confidence = c->w.confidence.as<float>();
   V.bgDisp = c->frame().bg[L].as<float>();
-  V.fovMask = c->w.fovMask.as<uint8_t>();
+  V.fovMask = c->fovMask.as<uint8_t>();
   V.pairCount = c->w.pairCount.as<uint8_t>();
   V.counters = counter_slot(c, stage, L);
 #if DERP_BLOCK_TRACE
@@ -390,10 +390,16 @@ int compute_fov_and_masks(derp_ctx* c, int level) {
   const size_t n = (size_t)W * H;
   {
     Span sp(c, ST_FOV, level);
-    hipLaunchKernelGGL(k_fov_mask, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>(), W, H,
-                       c->w.fovMask.as<uint8_t>());
-    KCHECK(c);
-    hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), c->D), dim3(256), 0, c->stream, c->w.fovMask.as<uint8_t>(),
+    // the FOV masks depend on the rig and the level size only, like the projection warps, and follow their rule
+    // (rebuild_warp_tables, warpCachedLevel): the first frame of a level builds them into the context's buffer, the
+    // other frames of the level, on the work lanes too, read them there. fov & fg stays per frame.
+    if (c->opt.rebuild_warp_tables || c->fovCachedLevel != level) {
+      hipLaunchKernelGGL(k_fov_mask, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>(), W, H,
+                         c->fovMask.as<uint8_t>());
+      KCHECK(c);
+      c->fovCachedLevel = level;
+    }
+    hipLaunchKernelGGL(k_and_masks, dim3(flat_grid(n), c->D), dim3(256), 0, c->stream, c->fovMask.as<uint8_t>(),
                        c->frame().fg[level].as<uint8_t>(), c->dst2src.as<int>(), 0, n, c->w.maskAnd.as<uint8_t>());
     KCHECK(c);
   }
@@ -519,8 +525,11 @@ int run_brute_force(derp_ctx* c, int dst0, int nd) {
   const int tilesX = std::max(1, (V.W - 2 + 7) / 8), tilesY = std::max(1, (V.H - 2 + 7) / 8);
   const int tiles = tilesX * tilesY;
   const size_t lds = kCostLdsPerSrc * (size_t)(c->S);
-  hipLaunchKernelGGL(k_brute_costs, dim3(tiles, kNumDepths, nd), dim3(kCostBlock), lds, c->stream, V,
-                     c->w.bruteCost.as<float>(), c->w.bruteConf.as<float>(), tilesX, tiles);
+  // one wave per (strip, run of disparity indices, destination): 49 x 15 x 16 at the 16-camera rig's 50 x 50 level with runs
+  // of 10, times the frames on the work lanes — still far above the chip's 4096 wave slots
+  const int run = std::min(std::max(c->bruteRun, 1), kNumDepths);
+  hipLaunchKernelGGL(k_brute_costs, dim3(tiles, (kNumDepths + run - 1) / run, nd), dim3(kCostBlock), lds, c->stream, V,
+                     c->w.bruteCost.as<float>(), c->w.bruteConf.as<float>(), tilesX, tiles, run);
   KCHECK(c);
   hipLaunchKernelGGL(k_brute_select, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->w.bruteCost.as<float>(),
                      c->w.bruteConf.as<float>());
@@ -563,7 +572,6 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
   Span sp(c, ST_PINGPONG, L);
   LevelView V = make_view(c, ST_PINGPONG, dst0, nd);
   const size_t n = (size_t)V.W * V.H;
-  HIPCHK(c, hipMemsetAsync(c->w.changed.as<uint8_t>() + (size_t)dst0 * n, 1, n * nd, c->stream));
   int tilesX;
   const int tiles = tiles_of(V.W, V.H, tilesX);
   const size_t lds = lds_for_waves(kCostLdsPerSrc * (size_t)(c->S), c->ppWaves, c->ldsPerCu, kCostLdsStatic);
@@ -573,20 +581,33 @@ int run_ping_pong(derp_ctx* c, int dst0, int nd) {
                           ? (c->ppCompact ? (four ? k_ping_pong_walk : k_ping_pong_walk_w3) : (four ? k_ping_pong_loop_walk : k_ping_pong_loop_walk_w3))
                           : (c->ppCompact ? (four ? k_ping_pong : k_ping_pong_w3) : (four ? k_ping_pong_loop : k_ping_pong_loop_w3));
   TRY(block_trace_attach(c, V, 1, cg.blocks, nd));
-  for (int it = 1; it <= c->opt.ping_pong_iterations; ++it) {
-    hipLaunchKernelGGL(kernel, dim3(cg.blocks, nd), dim3(kCostBlock), lds,
-                       c->stream, V, c->w.changed.as<uint8_t>(), c->w.dispRes.as<float>(), c->w.costRes.as<float>(), tilesX,
+  // Every iteration writes all pixels of its result planes, and `changed` = result != input for the next one (what the
+  // reference's commit does, Derp.cpp:527-529), so nothing is copied back: the odd iterations read disparity / cost and
+  // write dispRes / costRes, the even ones the other way round, and `changed` alternates between the two halves of its
+  // buffer — none before the first iteration (null: every pixel counts as changed). The memoised candidate is read in the
+  // first iteration only, from cost / confidence / pairCount as random proposals left them.
+  float* dispBuf[2] = {c->w.disparity.as<float>(), c->w.dispRes.as<float>()};
+  float* costBuf[2] = {c->w.cost.as<float>(), c->w.costRes.as<float>()};
+  uint8_t* chgBuf[2] = {c->w.changed.as<uint8_t>(), c->w.changed.as<uint8_t>() + n * c->D};
+  const int iterations = c->opt.ping_pong_iterations;
+  for (int it = 1; it <= iterations; ++it) {
+    const int from = (it - 1) & 1, to = it & 1;
+    V.disparity = dispBuf[from];
+    V.cost = costBuf[from];
+    hipLaunchKernelGGL(kernel, dim3(cg.blocks, nd), dim3(kCostBlock), lds, c->stream, V,
+                       it == 1 ? (const uint8_t*)nullptr : chgBuf[from], chgBuf[to], dispBuf[to], costBuf[to], tilesX,
                        (int)(it == 1 && c->randomRanThisLevel && !c->noMemo), cg.bands, cg.perBlock);
     KCHECK(c);
-    hipLaunchKernelGGL(k_ping_pong_commit, dim3(flat_grid(n * nd)), dim3(256), 0, c->stream,
-                       c->w.disparity.as<float>() + (size_t)dst0 * n, c->w.cost.as<float>() + (size_t)dst0 * n,
-                       c->w.dispRes.as<float>() + (size_t)dst0 * n, c->w.costRes.as<float>() + (size_t)dst0 * n,
-                       c->w.changed.as<uint8_t>() + (size_t)dst0 * n, n * nd);
-    KCHECK(c);
   }
-  // cost / confidence now belong to ping-pong's result (+inf where every candidate was rejected): the
-  // memoised candidate must not be served from them by a later derp_stage_ping_pong call
   if (dst0 + nd >= c->D) {
+    // the last batch is through: every batch ran the same number of iterations, so after an odd number all of them left
+    // their results in dispRes / costRes, which now become the working disparity and cost
+    if (iterations > 0 && (iterations & 1)) {
+      std::swap(c->w.disparity, c->w.dispRes);
+      std::swap(c->w.cost, c->w.costRes);
+    }
+    // cost / confidence now belong to ping-pong's result (+inf where every candidate was rejected): the
+    // memoised candidate must not be served from them by a later derp_stage_ping_pong call
     c->randomRanThisLevel = false;
   }
   return 0;
@@ -632,6 +653,24 @@ size_t bilateral_lds_bytes(int radius) {
 // what a block of k_joint_bilateral may ask for: 64 KiB less the kernel's own 256 B (its exp table)
 constexpr size_t kBilateralMaxLds = 64 * 1024 - 256;
 
+// The preconditions of k_joint_bilateral's FAST_TAP form with a u16 guide (bilateral_tap_fast): unit second and third
+// weights, a first weight in [0, inf), and 0 < 2 sigma^2 < inf as the kernel computes it
+bool bilateral_fast_tap_ok(float sigma, float w0, float w1, float w2) {
+  const float denom = 2.0f * (sigma * sigma);
+  return w1 == 1.0f && w2 == 1.0f && w0 >= 0.0f && std::isfinite(w0) && denom > 0.0f && std::isfinite(denom);
+}
+
+// the tiled kernel with a u16 guide, in the form its parameters allow: the same bits either way
+void launch_joint_bilateral_u16_tiled(derp_ctx* c, dim3 grid, const float* image, const void* guide, const uint8_t* mask,
+                                      int W, int H, int radius, float sigma, float w0, float w1, float w2, float* out,
+                                      size_t planeStride, size_t guideStride, const int* guideIndex) {
+  // (the fast form's block vote takes another 256 B of static LDS: the largest tiles, radius 22, leave no room for it)
+  const bool fast = bilateral_fast_tap_ok(sigma, w0, w1, w2) && bilateral_lds_bytes(radius) + 256 <= kBilateralMaxLds;
+  const auto kernel = fast ? k_joint_bilateral<true, true> : k_joint_bilateral<true, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), bilateral_lds_bytes(radius), c->stream, image, guide, mask, W, H, radius, sigma,
+                     w0, w1, w2, out, planeStride, guideStride, guideIndex);
+}
+
 int run_bilateral(derp_ctx* c) {
   const int L = c->cur;
   Span sp(c, ST_BILATERAL, L);
@@ -640,16 +679,19 @@ int run_bilateral(derp_ctx* c) {
   const size_t n = (size_t)W * H;
   // weights passed (B, G, R) = (0.5, 1, 1) — Derp.cpp:893-896, Derp.h:44-48; sigma 0.005
   const int radius = bilateral_radius(L);
-  hipLaunchKernelGGL(k_joint_bilateral<true>, dim3((W + 15) / 16, (H + 15) / 16, c->D), dim3(256),
-                     bilateral_lds_bytes(radius), c->stream, c->w.disparity.as<float>(),
-                     (const void*)c->frame().color[L].as<ushort4>(), c->w.maskAnd.as<uint8_t>(), W, H, radius, 0.005f, 0.5f,
-                     1.0f, 1.0f, c->w.tmpF.as<float>(), n, n, c->dst2src.as<int>());
+  launch_joint_bilateral_u16_tiled(c, dim3((W + 15) / 16, (H + 15) / 16, c->D), c->w.disparity.as<float>(),
+                                   (const void*)c->frame().color[L].as<ushort4>(), c->w.maskAnd.as<uint8_t>(), W, H, radius,
+                                   0.005f, 0.5f, 1.0f, 1.0f, c->w.tmpF.as<float>(), n, n, c->dst2src.as<int>());
   KCHECK(c);
-  HIPCHK(c, hipMemcpyAsync(c->w.disparity.p, c->w.tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  // the filtered planes become the working disparity: the two buffers exchange roles (both hold D planes of the
+  // largest level), nothing is copied back
+  std::swap(c->w.disparity, c->w.tmpF);
   return 0;
 }
 
-int run_median(derp_ctx* c, bool fuseMaskFov) {
+// `levelOut`: the level loop's last stage writes the frame's level (frame().disp[L]) itself and the level is complete;
+// as a stage of its own (null) the result becomes the working disparity, like the bilateral filter's
+int run_median(derp_ctx* c, bool fuseMaskFov, float* levelOut = nullptr) {
   const int L = c->cur;
   Span sp(c, ST_MEDIAN, L);
   c->randomRanThisLevel = false;  // the working disparity changes: cost[] no longer matches it
@@ -657,19 +699,21 @@ int run_median(derp_ctx* c, bool fuseMaskFov) {
   const size_t n = (size_t)W * H;
   hipLaunchKernelGGL(k_masked_median, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->w.disparity.as<float>(),
                      c->opt.use_foreground_masks ? c->frame().bg[L].as<float>() : (const float*)nullptr,
-                     c->w.maskAnd.as<uint8_t>(), W, H, 1, c->w.tmpF.as<float>(), n,
-                     fuseMaskFov ? c->w.fovMask.as<uint8_t>() : (const uint8_t*)nullptr);
+                     c->w.maskAnd.as<uint8_t>(), W, H, 1, levelOut ? levelOut : c->w.tmpF.as<float>(), n,
+                     fuseMaskFov ? c->fovMask.as<uint8_t>() : (const uint8_t*)nullptr);
   KCHECK(c);
-  HIPCHK(c, hipMemcpyAsync(c->w.disparity.p, c->w.tmpF.p, n * c->D * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  if (!levelOut) {
+    std::swap(c->w.disparity, c->w.tmpF);
+  }
   return 0;
 }
 
-int run_mask_fov(derp_ctx* c) {
+int run_mask_fov(derp_ctx* c, float* levelOut = nullptr) {
   const int L = c->cur;
   Span sp(c, ST_MASKFOV, L);
   const size_t n = npx(c, L) * c->D;
   hipLaunchKernelGGL(k_mask_fov, dim3(flat_grid(n)), dim3(256), 0, c->stream, c->w.disparity.as<float>(),
-                     c->w.fovMask.as<uint8_t>(), n);
+                     c->fovMask.as<uint8_t>(), levelOut ? levelOut : c->w.disparity.as<float>(), n);
   KCHECK(c);
   return 0;
 }
@@ -715,7 +759,12 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   // fresh PyramidLevel: disparity / cost / confidence start at 0 (PyramidLevel.h:209-221)
   HIPCHK(c, hipMemsetAsync(c->w.cost.p, 0, n * c->D * sizeof(float), c->stream));
   HIPCHK(c, hipMemsetAsync(c->w.confidence.p, 0, n * c->D * sizeof(float), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->w.mismatchMask.p, 0, n * c->D, c->stream));
+  // the mismatch mask is written by run_mismatches alone, under this condition: a level without the stage holds none
+  // (derp_download_mismatch_mask then answers zeros) and needs no clear
+  c->w.mismatchMaskHeld = level <= c->opt.mismatches_start_level && level != c->numLevels - 1;
+  if (c->w.mismatchMaskHeld) {
+    HIPCHK(c, hipMemsetAsync(c->w.mismatchMask.p, 0, n * c->D, c->stream));
+  }
   if (level < c->numLevels - 1 && !c->frame().haveDisp[level + 1] && !buildAllTables) {
     return fail(c, "Missing disparity of level %d needed to start level %d", level + 1, level);
   }
@@ -829,12 +878,14 @@ int process_level(derp_ctx* c, int level) {
   if (c->opt.do_bilateral_filter) {
     TRY(run_bilateral(c));
   }
+  // the last stage writes the frame's level itself: no copy of the working disparity at the end (level_end)
+  float* levelOut = c->frame().disp[level].as<float>();
   if (c->opt.do_median_filter) {
-    TRY(run_median(c, true));
+    TRY(run_median(c, true, levelOut));
   } else {
-    TRY(run_mask_fov(c));
+    TRY(run_mask_fov(c, levelOut));
   }
-  TRY(level_end(c));
+  c->frame().haveDisp[level] = 1;
   return 0;
 }
 
@@ -883,12 +934,11 @@ int alloc_pyramid(derp_ctx* c, FramePyramid& f) {
 int alloc_work_set(derp_ctx* c, WorkSet& w, size_t n) {
   ALLOC(c, w.srcVar, n * c->S * sizeof(float));
   ALLOC(c, w.ownBias, n * c->S * sizeof(ushort4));
-  ALLOC(c, w.fovMask, n * c->D);
   ALLOC(c, w.maskAnd, n * c->D);
   for (DevBuf* b : {&w.disparity, &w.cost, &w.confidence, &w.dispRes, &w.costRes, &w.tmpF, &w.rank}) {
     ALLOC(c, *b, n * c->D * sizeof(float));
   }
-  ALLOC(c, w.changed, n * c->D);
+  ALLOC(c, w.changed, 2 * n * c->D);  // ping-pong's `changed` of the iteration before and of this one
   ALLOC(c, w.mismatchMask, n * c->D);
   ALLOC(c, w.pairCount, n * c->D);
   return 0;
@@ -1041,6 +1091,9 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
     c->costTilesPerBlock = atoi(e);
   }
   c->noMemo = getenv("DERP_NO_MEMO") != nullptr;
+  if (const char* e = getenv("DERP_BRUTE_RUN")) {
+    c->bruteRun = atoi(e);
+  }
   if (const char* e = getenv("DERP_PP_COMPACT")) {
     c->ppCompact = atoi(e) != 0;
   }
@@ -1168,8 +1221,10 @@ int derp_set_pyramid(derp_ctx* c, int num_levels, const int* widths, const int* 
     nmax = std::max(nmax, npx(c, l));
   }
   TRY(alloc_work_set(c, c->w, nmax));
+  ALLOC(c, c->fovMask, nmax * c->D);
   c->cur = -1;
   c->warpCachedLevel = -1;
+  c->fovCachedLevel = -1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1509,6 +1564,10 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
     return fail(c, "bad destination index / null output");
   }
   const size_t n = npx(c, c->cur);
+  if (!c->w.mismatchMaskHeld) {  // no mismatch stage at this level: nothing was flagged (level_begin)
+    memset(out, 0, n);
+    return 0;
+  }
   return download_sync(c, out, c->w.mismatchMask.as<uint8_t>() + (size_t)d * n, n);
 }
 

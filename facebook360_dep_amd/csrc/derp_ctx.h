@@ -47,11 +47,12 @@ struct AreaTabDev {  // computeResizeAreaTab of one axis, resident in HBM
 // Everything processLevel writes per frame. The context has one and every work lane has one; the rig-only tables of a
 // level (projWarp, projWarpInv, rayDir, behind, resampling tables) are shared by the lanes and stay on the context.
 struct WorkSet {
-  DevBuf srcVar, ownBias, fovMask, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
+  DevBuf srcVar, ownBias, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
   DevBuf tileSeen;    // k_reproject_bias: per (table, tile) whether any map position is valid
   DevBuf projColor, projBias;
   DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)
   DevBuf bruteCost, bruteConf, lanczosTmp, staging, stagingB;
+  bool mismatchMaskHeld = false;   // mismatchMask was cleared for the current level (the mismatch stage runs at it)
   int colorTablesCleanLevel = -1;  // level whose colour / bias tables were written in full since its warps were built
 };
 
@@ -112,6 +113,8 @@ struct derp_ctx {
   DevBuf projWarp, projWarpInv;
   DevBuf rayDir, behind;  // per destination pixel: ray direction [3][D][n] f64, sources facing away [D][n] (k_pixel_rays)
   int warpCachedLevel = -1;
+  DevBuf fovMask;  // the destinations' FOV masks of level fovCachedLevel [D][n]: rig + level size only, shared by the lanes
+  int fovCachedLevel = -1;
   bool randomRanThisLevel = false;  // cost / confidence hold random-proposal results for this level
   bool tablesValid = false;
   std::map<std::pair<int, int>, LanczosTab> lanczos;  // (map nodes keep their addresses: get_lanczos / get_area_tab
@@ -143,6 +146,9 @@ struct derp_ctx {
   DevBuf blockTrace[2][kMaxLevels];
   int blockTraceGrid[2][kMaxLevels][2] = {};
   bool noMemo = false;  // DERP_NO_MEMO (developer switch), read once in derp_create
+  // consecutive disparity indices one block of k_brute_costs evaluates (DERP_BRUTE_RUN, developer A/B switch; same
+  // results for every length from 1 to 150), read once in derp_create
+  int bruteRun = 10;
   // ping-pong's candidate loop: compacted into full waves of (pixel, candidate) tasks, or one pixel per lane
   // (DERP_PP_COMPACT=0, developer A/B switch; same results), read once in derp_create
   bool ppCompact = true;

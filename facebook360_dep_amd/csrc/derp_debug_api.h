@@ -56,6 +56,23 @@ int derp_debug_fp64(derp_ctx* c, int op, const double* a, const double* b, doubl
   return 0;
 }
 
+int derp_debug_expf(derp_ctx* c, int mode, const float* x, float* out, size_t n) {
+  if (!c || !x || !out || mode < 0 || mode > 1) {
+    return fail(c, "bad arguments");
+  }
+  if (n == 0) {
+    return 0;
+  }
+  ALLOC(c, c->w.staging, 2 * n * sizeof(float));
+  float* d = c->w.staging.as<float>();
+  HIPCHK(c, hipMemcpyAsync(d, x, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_debug_expf, dim3(flat_grid(n)), dim3(256), 0, c->stream, mode, d, d + n, n);
+  KCHECK(c);
+  HIPCHK(c, hipMemcpyAsync(out, d + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int derp_debug_sees(derp_ctx* c, int src, const double* xyz, size_t n, double* out) {
   if (!c || !xyz || !out || src < 0 || src >= c->S) {
     return fail(c, "bad arguments");
@@ -84,7 +101,7 @@ int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
     return 0;
   }
   if (which == 5) {
-    HIPCHK(c, hipMemcpy(out, c->w.fovMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->fovMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
     return 0;
   }
   if (d < 0 || d >= c->D || s < 0 || s >= c->S || s == c->dst2srcH[d]) {

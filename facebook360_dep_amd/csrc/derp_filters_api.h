@@ -131,8 +131,12 @@ static void launch_joint_bilateral(derp_ctx* c, const float* image, const void* 
   const size_t n = (size_t)w * h;
   const dim3 grid((w + 15) / 16, (h + 15) / 16, 1);
   if (bilateral_lds_bytes(radius) <= kBilateralMaxLds) {
-    hipLaunchKernelGGL(k_joint_bilateral<GUIDE_U16>, grid, dim3(256), bilateral_lds_bytes(radius), c->stream, image, guide,
-                       mask, w, h, radius, sigma, w0, w1, w2, out, n, n, (const int*)nullptr);
+    if (GUIDE_U16) {  // the level loop's launcher: the fast tap where the parameters allow it
+      launch_joint_bilateral_u16_tiled(c, grid, image, guide, mask, w, h, radius, sigma, w0, w1, w2, out, n, n, nullptr);
+    } else {
+      hipLaunchKernelGGL(k_joint_bilateral<false>, grid, dim3(256), bilateral_lds_bytes(radius), c->stream, image, guide,
+                         mask, w, h, radius, sigma, w0, w1, w2, out, n, n, (const int*)nullptr);
+    }
   } else {
     hipLaunchKernelGGL(k_joint_bilateral_direct<GUIDE_U16>, grid, dim3(256), 0, c->stream, image, guide, mask, w, h,
                        radius, sigma, w0, w1, w2, out);

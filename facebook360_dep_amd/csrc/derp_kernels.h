@@ -1514,8 +1514,10 @@ __device__ __forceinline__ float probe_disparity(int i, float minD, float maxD) 
 }
 
 __global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
-    k_brute_costs(LevelView V, float* __restrict__ costs, float* __restrict__ confs, int tilesX, int tilesPerDst) {
-  const int i = blockIdx.y;   // disparity index
+    k_brute_costs(LevelView V, float* __restrict__ costs, float* __restrict__ confs, int tilesX, int tilesPerDst, int run) {
+  // a block evaluates `run` consecutive disparity indices for its strip: the window, the atan table, the pixel's constants
+  // and the cull ballots are paid once per block, not once per evaluation
+  const int i0 = blockIdx.y * run, i1 = min(i0 + run, kNumDepths);
   const int dl = blockIdx.z;
   const int d = V.dst0 + dl;
   // the coarsest level is small (50 x 50): interior pixels are numbered densely in 8-wide strips of
@@ -1531,19 +1533,40 @@ __global__ void __launch_bounds__(kCostBlock, DERP_COST_MIN_WAVES)
     const int own = V.dst2src[d];
     const size_t n = (size_t)V.W * V.H, idx = (size_t)y * V.W + x;
     const float minDisparity = 1.0f / V.maxDepthM, maxDisparity = 1.0f / V.minDepthM;
-    const float disparity = probe_disparity(i, minDisparity, maxDisparity);
     const bool fov = V.fovMask[(size_t)d * n + idx], fg = V.srcFg[(size_t)own * n + idx];
-    const bool closer = V.hasFg ? (V.bgDisp[(size_t)d * n + idx] < disparity) : true;
-    float2 r = make_float2(__builtin_nanf(""), __builtin_nanf(""));
-    if (fov && fg && closer) {
+    const float nan = __builtin_nanf("");
+    if (fov && fg) {
       PixCtx px;
-      load_pixctx(V, d, own, x, y, win, px);
-      r = compute_cost(V, dl, own, px, disparity, pairs, nPair);
-      ++nCost;
+      load_pixctx<false>(V, d, own, x, y, win, px);
+      // the sources that every evaluating pixel of the strip has behind it at any depth >= kCullMinDepth: exact, and
+      // compute_cost switches the mask off by itself for a candidate nearer than that (a small --min_depth)
+      const unsigned cull = behind_sources(V, d, idx);
+      // what the run carries per lane: the pixel, as in ping-pong's candidate loop; the rest is derived again per index
+      const unsigned xy = (unsigned)x | ((unsigned)y << 16);
+      for (int i = i0; i < i1; ++i) {
+        unsigned q = xy;
+        asm("" : "+v"(q) : "s"(i));
+        const unsigned pidx = (q >> 16) * (unsigned)V.W + (q & 0xffffu);
+        const float disparity = probe_disparity(i, minDisparity, maxDisparity);
+        const bool closer = V.hasFg ? ((V.bgDisp + (size_t)d * n)[pidx] < disparity) : true;
+        float2 r = make_float2(nan, nan);
+        if (closer) {
+          unsigned np = 0;
+          r = compute_cost<false, true>(V, dl, own, px, disparity, pairs, np, cull, pidx);
+          nPair += np;
+          ++nCost;
+        }
+        const size_t o = ((size_t)dl * kNumDepths + i) * n;
+        (costs + o)[pidx] = r.x;
+        (confs + o)[pidx] = r.y;
+      }
+    } else {
+      for (int i = i0; i < i1; ++i) {
+        const size_t o = ((size_t)dl * kNumDepths + i) * n + idx;
+        costs[o] = nan;
+        confs[o] = nan;
+      }
     }
-    const size_t o = ((size_t)dl * kNumDepths + i) * n + idx;
-    costs[o] = r.x;
-    confs[o] = r.y;
   }
   flush_counters(V, nCost, nPair);
 }
@@ -1846,7 +1869,8 @@ __device__ __forceinline__ void ping_pong_candidates_loop(const LevelView& V, co
   const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
   const float* disp = V.disparity + (size_t)d * n;
   const uint8_t* fov = V.fovMask + (size_t)d * n;
-  const uint8_t* chg = changed + (size_t)d * n;
+  const bool allChanged = changed == nullptr;  // (wave-uniform) the first iteration: no plane to read
+  const uint8_t* chg = allChanged ? nullptr : changed + (size_t)d * n;
   outDisp = disp[idx];
   const bool interior = x >= 1 && y >= 1 && x < V.W - 1 && y < V.H - 1;
   if (interior && fov[idx]) {
@@ -1873,7 +1897,7 @@ __device__ __forceinline__ void ping_pong_candidates_loop(const LevelView& V, co
         if (fov[j]) {
           const float cand = disp[j];
           const float bg = V.hasFg ? (V.bgDisp + (size_t)d * n)[pidx] : 0.f;
-          if (cand >= bg && chg[j]) {
+          if (cand >= bg && (allChanged || chg[j])) {
             float2 r;
             // Candidate (0,0) is the pixel's own disparity. In the first iteration, where random
             // proposals evaluated this pixel, computeCost(own disparity) is exactly the value they
@@ -1925,7 +1949,8 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
   const int lane = (int)(threadIdx.x & 63);
   const float* disp = V.disparity + (size_t)d * n;
   const uint8_t* fov = V.fovMask + (size_t)d * n;
-  const uint8_t* chg = changed + (size_t)d * n;
+  const bool allChanged = changed == nullptr;  // (wave-uniform) the first iteration: no plane to read
+  const uint8_t* chg = allChanged ? nullptr : changed + (size_t)d * n;
   // 1. owner pass
   unsigned cmask = 0;
   bool eval = false;
@@ -1945,7 +1970,7 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
           const unsigned j = (unsigned)yy * (unsigned)V.W + (unsigned)xx;
           if (fov[j]) {
             const float cand = disp[j];
-            if (cand >= bg && chg[j]) {
+            if (cand >= bg && (allChanged || chg[j])) {
               const float memoConf = (k == 0 && useMemo) ? (V.confidence + (size_t)d * n)[idx] : 0.0f;
               if (memoConf != 0.0f) {
                 const float c = (V.cost + (size_t)d * n)[idx];
@@ -2055,9 +2080,9 @@ __device__ __forceinline__ void ping_pong_candidates_compact(const LevelView& V,
 
 // One tile of a ping-pong iteration; every lane of the wave takes part.
 template <bool COMPACT>
-__device__ __forceinline__ void ping_pong_tile(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                                               float* __restrict__ costRes, int dl, int x, int y, const PatchWin* win, LdsPairs& pairs,
-                                               int useMemo) {
+__device__ __forceinline__ void ping_pong_tile(const LevelView& V, const uint8_t* __restrict__ changed, uint8_t* __restrict__ changedNext,
+                                               float* __restrict__ dispRes, float* __restrict__ costRes, int dl, int x, int y,
+                                               const PatchWin* win, LdsPairs& pairs, int useMemo) {
   const int d = V.dst0 + dl;
   // per-lane counters in one register: pairs (bits 0..15: <= 10 * 31), cost evaluations (16..23: <= 10), memoised (24..)
   unsigned counts = 0, fillSlots = 0;
@@ -2076,6 +2101,8 @@ __device__ __forceinline__ void ping_pong_tile(const LevelView& V, const uint8_t
     const unsigned idx = (unsigned)y * (unsigned)V.W + (unsigned)x;
     (dispRes + (size_t)d * n)[idx] = outDisp;
     (costRes + (size_t)d * n)[idx] = outCost;
+    // changed = disp != dispRes (Derp.cpp:527-529), for the next iteration: on the value just stored and the one it replaces
+    (changedNext + (size_t)d * n)[idx] = (V.disparity + (size_t)d * n)[idx] != outDisp;
   }
 #if DERP_PHASE_TIMERS
   if ((threadIdx.x & 63) == 0) {
@@ -2104,8 +2131,9 @@ __device__ __forceinline__ void ping_pong_tile(const LevelView& V, const uint8_t
 // The block walks `perBlock` consecutive tiles like random proposals' (random_proposals_body): the atan table once, the
 // window per tile, nothing per lane carried from one tile to the next.
 template <bool COMPACT, bool WALK>
-__device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes,
-                                               float* __restrict__ costRes, int tilesX, int useMemo, int bands, int perBlock) {
+__device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t* __restrict__ changed, uint8_t* __restrict__ changedNext,
+                                               float* __restrict__ dispRes, float* __restrict__ costRes, int tilesX, int useMemo,
+                                               int bands, int perBlock) {
   const unsigned long long bt0 = block_trace_begin();
   const int steps = WALK ? perBlock : 1;
   const int dl = blockIdx.y;
@@ -2117,7 +2145,7 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
     int x, y;
     tile_pixel(cost_block_tile(blockIdx.x, gridDim.x, V.xcdRotate ? d : 0, bands, steps, step), tilesX, x, y);
     cost_tile_prologue(V, d, x - (int)(threadIdx.x & 7), y - (int)((threadIdx.x & 63) >> 3), win, pairs, lutReady);
-    ping_pong_tile<COMPACT>(V, changed, dispRes, costRes, dl, x, y, win, pairs, useMemo);
+    ping_pong_tile<COMPACT>(V, changed, changedNext, dispRes, costRes, dl, x, y, win, pairs, useMemo);
   }
   block_trace_end(V, bt0);
 }
@@ -2126,9 +2154,9 @@ __device__ __forceinline__ void ping_pong_body(const LevelView& V, const uint8_t
 // loop it replaced (DERP_PP_COMPACT=0, developer A/B). The launcher picks (run_ping_pong, derp_capi.hip).
 #define DERP_PING_PONG_KERNEL(NAME, WAVES, COMPACT, WALK)                                                                   \
   __global__ void __launch_bounds__(kCostBlock, WAVES)                                                                      \
-      NAME(LevelView V, const uint8_t* __restrict__ changed, float* __restrict__ dispRes, float* __restrict__ costRes,     \
-           int tilesX, int useMemo, int bands, int perBlock) {                                                              \
-    ping_pong_body<COMPACT, WALK>(V, changed, dispRes, costRes, tilesX, useMemo, bands, perBlock);                          \
+      NAME(LevelView V, const uint8_t* __restrict__ changed, uint8_t* __restrict__ changedNext, float* __restrict__ dispRes, \
+           float* __restrict__ costRes, int tilesX, int useMemo, int bands, int perBlock) {                                 \
+    ping_pong_body<COMPACT, WALK>(V, changed, changedNext, dispRes, costRes, tilesX, useMemo, bands, perBlock);             \
   }
 DERP_PING_PONG_KERNEL(k_ping_pong, DERP_COST_MIN_WAVES, true, false)
 DERP_PING_PONG_KERNEL(k_ping_pong_w3, 3, true, false)  // more than 16 cameras: see k_random_proposals_w3
@@ -2140,19 +2168,6 @@ DERP_PING_PONG_KERNEL(k_ping_pong_walk_w3, 3, true, true)
 DERP_PING_PONG_KERNEL(k_ping_pong_loop_walk, DERP_COST_MIN_WAVES, false, true)
 DERP_PING_PONG_KERNEL(k_ping_pong_loop_walk_w3, 3, false, true)
 #undef DERP_PING_PONG_KERNEL
-
-// changed = disp != dispRes; dispRes -> disp; costRes -> cost (Derp.cpp:527-529)
-__global__ void k_ping_pong_commit(float* __restrict__ disp, float* __restrict__ cost, const float* __restrict__ dispRes,
-                                   const float* __restrict__ costRes, uint8_t* __restrict__ changed, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t step = (size_t)gridDim.x * blockDim.x;
-  for (; i < n; i += step) {
-    const float a = disp[i], b = dispRes[i];
-    changed[i] = (a != b);
-    disp[i] = b;
-    cost[i] = costRes[i];
-  }
-}
 
 // ----------------------------------------------------------------------------------------
 // handleDisparityMismatches — Derp.cpp:553-748 (off unless level <= --mismatches_start_level).
@@ -2311,11 +2326,28 @@ __device__ __forceinline__ float div_int_by_const(int y, double rcp) {
 }
 
 // `tab` = kExp2fTab staged in LDS by the caller (a divergent __constant__ index would be a global load per call)
-__device__ __forceinline__ float expf_glibc(float x, const unsigned long long* tab) {
+// what expf does with an argument that passed its range tests
+__device__ __forceinline__ float expf_glibc_poly(float x, const unsigned long long* tab) {
   const double InvLn2N = 0x1.71547652b82fep+0 * 32;
   const double C0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32,
                C2 = 0x1.62e42ff0c52d6p-1 / 32;
   const double SHIFT = 0x1.8p+52;
+  const double xd = (double)x;
+  double kd = __builtin_fma(InvLn2N, xd, SHIFT);
+  const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
+  kd -= SHIFT;
+  const double r = __builtin_fma(InvLn2N, xd, -kd);
+  const unsigned long long t = tab[ki & 31] + (ki << 47);
+  const double sc = __longlong_as_double((long long)t);
+  const double z = __builtin_fma(C0, r, C1);
+  const double r2 = r * r;
+  double y = __builtin_fma(C2, r, 1.0);
+  y = __builtin_fma(z, r2, y);
+  y = y * sc;
+  return (float)y;
+}
+
+__device__ __forceinline__ float expf_glibc(float x, const unsigned long long* tab) {
   const unsigned abstop = (__float_as_uint(x) >> 20) & 0x7ff;
   if (abstop >= (0x42b00000u >> 20)) {  // |x| >= 88 or NaN
     if (__float_as_uint(x) == 0xff800000u) {
@@ -2331,19 +2363,31 @@ __device__ __forceinline__ float expf_glibc(float x, const unsigned long long* t
       return 0.0f;
     }
   }
-  const double xd = (double)x;
-  double kd = __builtin_fma(InvLn2N, xd, SHIFT);
-  const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
-  kd -= SHIFT;
-  const double r = __builtin_fma(InvLn2N, xd, -kd);
-  const unsigned long long t = tab[ki & 31] + (ki << 47);
-  const double sc = __longlong_as_double((long long)t);
-  const double z = __builtin_fma(C0, r, C1);
-  const double r2 = r * r;
-  double y = __builtin_fma(C2, r, 1.0);
-  y = __builtin_fma(z, r2, y);
-  y = y * sc;
-  return (float)y;
+  return expf_glibc_poly(x, tab);
+}
+
+// expf_glibc for an argument known to lie in [-inf, -0] and not to be NaN: of the range tests above only the underflow
+// one can fire. Below 88 in magnitude neither function tests anything. From 88 up, x is not NaN and not +inf, x > 88.7
+// is false for x <= -0, and -inf returns 0 from the first test there and from `x < -0x1.9fe368p6f` here; every other
+// x reaches the same comparison and then the same polynomial. So the results are the same bits for every such x
+// (tests/test_gpu_bilateral_fast_tap.py compares the two over the edges of every branch and 10^7 random arguments).
+__device__ __forceinline__ float expf_glibc_nonpos(float x, const unsigned long long* tab) {
+  if (x < -0x1.9fe368p6f) {
+    return 0.0f;
+  }
+  return expf_glibc_poly(x, tab);
+}
+
+// mode 0: expf_glibc, 1: expf_glibc_nonpos (arguments in [-inf, -0] only)
+__global__ void __launch_bounds__(256) k_debug_expf(int mode, const float* __restrict__ x, float* __restrict__ out, size_t n) {
+  __shared__ unsigned long long expTab[32];
+  if (threadIdx.x < 32) {
+    expTab[threadIdx.x] = kExp2fTab[threadIdx.x];
+  }
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    out[i] = mode == 0 ? expf_glibc(x[i], expTab) : expf_glibc_nonpos(x[i], expTab);
+  }
 }
 
 // generalizedJointBilateralFilter — TemporalBilateralFilter.h:39-124. One 16x16 pixel tile per
@@ -2377,12 +2421,29 @@ __device__ __forceinline__ void bilateral_tap(float4 centre, float4 t, float wei
   weightedAvg += weight * t.w;
 }
 
-template <bool GUIDE_U16>
+// The tap for the parameters the level loop passes, chosen by the host per launch (bilateral_fast_tap_ok):
+//   weight1 == weight2 == 1: 1.0f * x is x for every float x (NaN payloads included), so the two products go;
+//   u16 guide, 0 <= weight0 < inf, 0 < 2 sigma^2 < inf: the guide differences are finite, so colorDiffSq is a sum of
+//   non-negative finite terms, in [+0, +inf] and not NaN. -colorDiffSq is then in [-inf, -0]; the two quotients multiply it
+//   by the positive finite doubles 1/3 and 1/denom and round, which keeps it in [-inf, -0]. That is expf_glibc_nonpos's
+//   precondition, under which it returns expf_glibc's bits.
+__device__ __forceinline__ void bilateral_tap_fast(float4 centre, float4 t, float weight0, double rcpDenom,
+                                                   const unsigned long long* expTab, float& sumWeight, float& weightedAvg) {
+  const float d0 = centre.x - t.x, d1 = centre.y - t.y, d2 = centre.z - t.z;
+  const float colorDiffSq = weight0 * (d0 * d0) + (d1 * d1) + (d2 * d2);
+  const float weight = expf_glibc_nonpos(div_by_const(div_by_const(-colorDiffSq, 1.0 / 3.0), rcpDenom), expTab);
+  sumWeight += weight;
+  weightedAvg += weight * t.w;
+}
+
+// FAST_TAP: bilateral_tap_fast for every tap, and a block whose staged tile has every mask byte set reads no mask per tap
+template <bool GUIDE_U16, bool FAST_TAP = false>
 __global__ void __launch_bounds__(256)
     k_joint_bilateral(const float* __restrict__ image, const void* __restrict__ guideV,
                       const uint8_t* __restrict__ mask, int W, int H, int radius, float sigma, float weight0,
                       float weight1, float weight2, float* __restrict__ out, size_t planeStride, size_t guideStride,
                       const int* __restrict__ guideIndex) {
+  static_assert(GUIDE_U16 || !FAST_TAP, "the fast tap's range argument needs the u16 guide");
   extern __shared__ float ldsTile[];
   __shared__ unsigned long long expTab[32];
   if (threadIdx.x < 32) {
@@ -2403,15 +2464,23 @@ __global__ void __launch_bounds__(256)
   const uint8_t* m = mask + (size_t)p * planeStride;
   const size_t gplane = (size_t)(guideIndex ? guideIndex[p] : p) * guideStride;
   const int x0 = blockIdx.x * 16 - radius, y0 = blockIdx.y * 16 - radius;
+  int staged = 1;  // every mask byte this thread staged is set
   for (int k = threadIdx.x; k < T * T; k += 256) {
     const int ty = k / T, tx = k - ty * T;
     const int i = ty * P + tx;
     const int sx = min(max(x0 + tx, 0), W - 1), sy = min(max(y0 + ty, 0), H - 1);
     const size_t j = (size_t)sy * W + sx;
-    tMask[i] = m[j];
+    const uint8_t mk = m[j];
+    staged &= mk != 0;
+    tMask[i] = mk;
     tTex[i] = bilateral_texel<GUIDE_U16>(guideV, gplane + j, img[j]);
   }
-  __syncthreads();
+  bool fullMask = false;
+  if (FAST_TAP) {
+    fullMask = __syncthreads_and(staged) != 0;
+  } else {
+    __syncthreads();
+  }
   const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
   const int x = blockIdx.x * 16 + lx, y = blockIdx.y * 16 + ly;
   if (x >= W || y >= H) {
@@ -2424,14 +2493,27 @@ __global__ void __launch_bounds__(256)
     const float denom = 2.0f * (sigma * sigma);
     const double rcpDenom = 1.0 / (double)denom;
     float sumWeight = 0.f, weightedAvg = 0.f;
-    for (int v = -radius; v <= radius; ++v) {
-      const int row = c + v * P;
-      for (int u = -radius; u <= radius; ++u) {
-        const int j = row + u;
-        if (!tMask[j]) {
-          continue;
+    if (FAST_TAP && fullMask) {  // (block-uniform) no tap is masked: the same taps in the same order, no mask reads
+      for (int v = -radius; v <= radius; ++v) {
+        const int row = c + v * P;
+        for (int u = -radius; u <= radius; ++u) {
+          bilateral_tap_fast(centre, tTex[row + u], weight0, rcpDenom, expTab, sumWeight, weightedAvg);
         }
-        bilateral_tap(centre, tTex[j], weight0, weight1, weight2, rcpDenom, expTab, sumWeight, weightedAvg);
+      }
+    } else {
+      for (int v = -radius; v <= radius; ++v) {
+        const int row = c + v * P;
+        for (int u = -radius; u <= radius; ++u) {
+          const int j = row + u;
+          if (!tMask[j]) {
+            continue;
+          }
+          if (FAST_TAP) {
+            bilateral_tap_fast(centre, tTex[j], weight0, rcpDenom, expTab, sumWeight, weightedAvg);
+          } else {
+            bilateral_tap(centre, tTex[j], weight0, weight1, weight2, rcpDenom, expTab, sumWeight, weightedAvg);
+          }
+        }
       }
     }
     if (sumWeight != 0.0f) {
@@ -2591,12 +2673,16 @@ __global__ void k_masked_median(const float* __restrict__ image, const float* __
   out[(size_t)p * planeStride + idx] = result;
 }
 
-__global__ void k_mask_fov(float* __restrict__ disp, const uint8_t* __restrict__ fov, size_t n) {
+// `out` is `disp` itself (in place: only the pixels outside the field of view are written) or another buffer
+__global__ void k_mask_fov(const float* disp, const uint8_t* __restrict__ fov, float* out, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t step = (size_t)gridDim.x * blockDim.x;
+  const bool inPlace = out == disp;
   for (; i < n; i += step) {
     if (!fov[i]) {
-      disp[i] = __builtin_nanf("");
+      out[i] = __builtin_nanf("");
+    } else if (!inPlace) {
+      out[i] = disp[i];
     }
   }
 }

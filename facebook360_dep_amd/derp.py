@@ -103,7 +103,7 @@ EXPORTS = [
     "derp_level_begin", "derp_stage_reproject_colors", "derp_stage_brute_force", "derp_stage_random_proposals",
     "derp_stage_ping_pong", "derp_stage_mismatches", "derp_stage_bilateral_filter", "derp_stage_median_filter", "derp_stage_mask_fov",
     "derp_level_end", "derp_set_level_disparity", "derp_get_level_disparity", "derp_cost_map", "derp_debug_download",
-    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees", "derp_debug_block_trace",
+    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees", "derp_debug_expf", "derp_debug_block_trace",
     "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
     "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
     "derp_render_vertices",
@@ -418,6 +418,14 @@ class Derp:
         assert b is None or b.shape == a.shape
         out = np.zeros_like(a)
         self._ck(lib().derp_debug_fp64(self.h, self.FP64_OPS[op], _p(a), _p(b), _p(out), C.c_size_t(a.size)))
+        return out
+
+    def debug_expf(self, x, nonpos=False):
+        """The filters' expf on the device, element by element: the full routine, or (nonpos) the form with one range
+        test that stands in for it on arguments in [-inf, -0]."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros_like(x)
+        self._ck(lib().derp_debug_expf(self.h, int(bool(nonpos)), _p(x), _p(out), C.c_size_t(x.size)))
         return out
 
     def debug_sees(self, src, xyz):

@@ -181,7 +181,9 @@ int derp_stage_bilateral_filter(derp_ctx* ctx);     /* bilateralFilter,        D
 int derp_stage_median_filter(derp_ctx* ctx);        /* medianFilter,           Derp.cpp:904-920  */
 int derp_stage_mask_fov(derp_ctx* ctx);             /* maskFov,                Derp.cpp:940-951  */
 int derp_level_end(derp_ctx* ctx);                  /* publish the level's disparity to the pyramid */
-/* set / read the working disparity of the current level (between stages) */
+/* set / read the working disparity of the current level (between stages). After derp_process_level the level's result is
+ * in the pyramid (derp_download_disparity): the loop's last stage writes it there, and the working disparity keeps what that
+ * stage read */
 int derp_set_level_disparity(derp_ctx* ctx, int dst, const float* disp);
 int derp_get_level_disparity(derp_ctx* ctx, int dst, float* disp);
 /* computeCost (Derp.cpp:104-226) of a caller-supplied disparity map at every interior pixel */
@@ -199,6 +201,9 @@ int derp_debug_fp64(derp_ctx* ctx, int op, const double* a, const double* b, dou
  * out[6 i .. 6 i + 5] = (vis, pix.x, pix.y) of the ping-pong / brute-force variant, then of the random-proposal variant,
  * for the rig points xyz[3 i .. 3 i + 2]; pix is NaN where the point lies outside the FOV cone */
 int derp_debug_sees(derp_ctx* ctx, int src, const double* xyz, size_t n, double* out);
+/* the filters' expf on the device: out[i] = mode 0 the full routine, 1 the form with the single range test that the joint
+ * bilateral filter's fast tap uses, which equals the full one for x[i] in [-inf, -0] */
+int derp_debug_expf(derp_ctx* ctx, int mode, const float* x, float* out, size_t n);
 
 /* developer builds (-DDERP_BLOCK_TRACE=1, tools/block_trace.py): {start, end} in 10 ns ticks of every block of the last
  * random-proposal ("random_proposals") / ping-pong ("ping_pong") launch of `level`, out[(y * grid_x + x) * 2 ..]; with

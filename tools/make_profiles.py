@@ -5,7 +5,7 @@ summaries (HBM bytes AND the SQ issue counters), the bench lines, and profiles/v
 bench.py reads for `roofline`.
 
 Counter handling, per /opt/skills/guides/MI355X_MICROARCH.md: FETCH_SIZE is doubled (gfx950 reports half the
-bytes; confirmed here on k_ping_pong_commit, whose reads are 3 x 4 B per pixel), WRITE_SIZE is taken as is;
+bytes; confirmed on the former commit kernel of ping-pong, whose reads were 3 x 4 B per pixel), WRITE_SIZE is taken as is;
 both are in KB. SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles (x 4 = cycles), summed over the
 chip. GRBM_GUI_ACTIVE counts cycles and is summed over the 8 XCDs (checked: value / 8 / launch duration =
 2.3-2.4 GHz), so the chip-busy cycles of a launch are GRBM_GUI_ACTIVE / 8. "level-0 launch" = the dispatch with the largest value of each counter
