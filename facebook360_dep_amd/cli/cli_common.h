@@ -747,6 +747,25 @@ inline void raster_to_bgr16(const Raster& p, const fs::path& path, uint16_t* out
     }
   }
 }
+// cv_util::loadImage<Vec4w> (CvUtil.h:196-284), GeometricConsistency's loadImages<Pixel>: like raster_to_bgr16, with the
+// file's alpha kept, or the largest value where it has none (COLOR_GRAY2BGRA / COLOR_BGR2BGRA)
+inline std::vector<uint16_t> load_color_bgra16(const fs::path& path, int& w, int& h) {
+  const Raster p = read_raster(path);
+  w = p.w;
+  h = p.h;
+  const size_t n = (size_t)w * h;
+  std::vector<uint16_t> bgr(n * 3), out(n * 4);
+  raster_to_bgr16(p, path, bgr.data());
+  const bool alpha = p.bitdepth != 32 && p.channels == 4;
+  const int mul = p.bitdepth == 8 ? 257 : 1;
+  for (size_t i = 0; i < n; ++i) {
+    out[4 * i] = bgr[3 * i];
+    out[4 * i + 1] = bgr[3 * i + 1];
+    out[4 * i + 2] = bgr[3 * i + 2];
+    out[4 * i + 3] = alpha ? (uint16_t)(p.px[p.channels * i + p.channels - 1] * mul) : (uint16_t)65535;
+  }
+  return out;
+}
 inline void load_color_bgr16_into(const fs::path& path, uint16_t* out, int expectW, int expectH) {
   const std::string data = read_file_or_empty(path);
   CHECK_MSG(!data.empty(), "failed to load image: " + path.string());

@@ -25,6 +25,7 @@
 #include "derp_mesh.h"
 #include "derp_points.h"
 #include "derp_render.h"
+#include "derp_geometric.h"
 
 using namespace derp;
 
@@ -252,11 +253,12 @@ int get_area_tab(derp_ctx* c, int ssize, int dsize, AreaTabDev** out, bool force
   return 0;
 }
 
-// cv2.resize(src, (dw, dh), INTER_AREA): kind 0 BGR u16 -> BGRX, 1 u8 (-> {0,1} when threshold >= 0), 2 f32
+// cv2.resize(src, (dw, dh), INTER_AREA): kind 0 BGR u16 -> BGRX, 1 u8 (-> {0,1} when threshold >= 0), 2 f32, 3 f32 x3,
+// 4 BGRA u16 -> BGRA int16 (k_resize_area)
 int resize_area_dev(derp_ctx* c, int kind, const void* src, int sw, int sh, void* dst, int dw, int dh, int threshold) {
   if (dw > sw || dh > sh) {
     // enlarging along an axis: cv::resize(INTER_AREA) turns into its bilinear emulation (float images only here)
-    if (kind < 2) {
+    if (kind < 2 || kind == 4) {
       return fail(c, "pyramid levels must not be larger than the full-size frame (%dx%d -> %dx%d)", sw, sh, dw, dh);
     }
     const dim3 g = grid2d(dw, dh, 1, kBlk2d);
@@ -287,6 +289,8 @@ int resize_area_dev(derp_ctx* c, int kind, const void* src, int sw, int sh, void
     hipLaunchKernelGGL(k_resize_area<1>, g, kBlk2d, 0, c->stream, src, sw, sh, dst, dw, dh, ax, ay, threshold);
   } else if (kind == 3) {
     hipLaunchKernelGGL(k_resize_area<3>, g, kBlk2d, 0, c->stream, src, sw, sh, dst, dw, dh, ax, ay, threshold);
+  } else if (kind == 4) {
+    hipLaunchKernelGGL(k_resize_area<4>, g, kBlk2d, 0, c->stream, src, sw, sh, dst, dw, dh, ax, ay, threshold);
   } else {
     hipLaunchKernelGGL(k_resize_area<2>, g, kBlk2d, 0, c->stream, src, sw, sh, dst, dw, dh, ax, ay, threshold);
   }
@@ -1577,6 +1581,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
 #include "derp_rephoto_api.h"
 #include "derp_points_api.h"
 #include "derp_mesh_api.h"
+#include "derp_geometric_api.h"
 #include "derp_filters_api.h"
 #include "derp_debug_api.h"
 #include "derp_sequence.h"

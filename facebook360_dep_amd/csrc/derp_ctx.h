@@ -22,12 +22,15 @@ enum Stage {
   ST_MASKFOV,
   ST_TEMPORAL,
   ST_LANES,  // wall of a level whose frames ran on overlapping work lanes (their per-stage spans overlap in time)
+  ST_GC_PREPARE,  // GeometricConsistency (derp_geometric_api.h), timed under level 0
+  ST_GC_SWEEP,
+  ST_GC_CLEAN,
   ST_COUNT
 };
 const char* kStageNames[ST_COUNT] = {"fov_mask",  "variance",    "own_bias",         "upsample",  "proj_warp",
                                      "reproject", "proj_bias",   "brute_force",      "random_proposals",
                                      "ping_pong", "mismatches",  "bilateral",        "median",    "mask_fov",
-                                     "temporal",  "lanes_wall"};
+                                     "temporal",  "lanes_wall", "gc_prepare",       "gc_sweep",  "gc_clean"};
 constexpr int kMaxLevels = 24;
 
 struct TimedSpan {
@@ -69,7 +72,7 @@ struct WorkLane {
 };
 
 // per tool family, defined in its derp_*_api.h and created by the family's first call that needs it
-struct SmrState; struct RephotoState; struct PointsState; struct MeshState;
+struct SmrState; struct RephotoState; struct PointsState; struct MeshState; struct GcState;
 
 }  // namespace
 
@@ -164,6 +167,7 @@ struct derp_ctx {
   std::unique_ptr<RephotoState> rephoto;
   std::unique_ptr<PointsState> points;
   std::unique_ptr<MeshState> mesh;
+  std::unique_ptr<GcState> gc;
 };
 
 namespace {

@@ -2813,6 +2813,8 @@ __global__ void k_spiral_fill(const float* __restrict__ dispUp, const float* __r
 //   KIND 2: f32 in -> f32 out                                     (background disparity)
 //   KIND 3: f32 x3 interleaved in -> f32 x3 interleaved out        (UpsampleDisparity's Vec3f colour guide,
 //           cv_util::resizeImage CvUtil.h:139-147; channels are independent in cv::resize)
+//   KIND 4: BGRA u16 interleaved in -> BGRA int16 (short4) out      (GeometricConsistency's computeReference: the u16
+//           result of the resize, then convertTo(CV_16S, 32767 / 65535.0): DESIGN §8.6)
 // ----------------------------------------------------------------------------------------
 struct AreaAxis {
   const int* start;    // [dsize + 1] first table entry of each output index
@@ -2825,6 +2827,8 @@ template <int KIND>
 __device__ __forceinline__ float area_src(const void* src, size_t pix, int c) {
   if (KIND == 0) {
     return (float)reinterpret_cast<const uint16_t*>(src)[pix * 3 + c];
+  } else if (KIND == 4) {
+    return (float)reinterpret_cast<const uint16_t*>(src)[pix * 4 + c];
   } else if (KIND == 1) {
     return (float)reinterpret_cast<const uint8_t*>(src)[pix];
   } else if (KIND == 3) {
@@ -2887,7 +2891,7 @@ __global__ void k_resize_area(const void* __restrict__ src, int SW, int SH, void
   if (dx >= DW || dy >= DH) {
     return;
   }
-  constexpr int CN = (KIND == 0 || KIND == 3) ? 3 : 1;
+  constexpr int CN = KIND == 4 ? 4 : (KIND == 0 || KIND == 3) ? 3 : 1;
   float res[CN];
   if (SW == DW && SH == DH) {
     for (int c = 0; c < CN; ++c) {
@@ -2942,6 +2946,13 @@ __global__ void k_resize_area(const void* __restrict__ src, int SW, int SH, void
     reinterpret_cast<ushort4*>(dst)[o] =
         make_ushort4((unsigned short)min(max(cv_round(res[0]), 0), 65535), (unsigned short)min(max(cv_round(res[1]), 0), 65535),
                      (unsigned short)min(max(cv_round(res[2]), 0), 65535), 0);
+  } else if (KIND == 4) {
+    short q[4];
+    for (int c = 0; c < CN; ++c) {
+      const double v = (double)min(max(cv_round(res[c]), 0), 65535) * (32767.0 / 65535.0);
+      q[c] = (short)fmin(fmax(rint(v), -32768.0), 32767.0);
+    }
+    reinterpret_cast<short4*>(dst)[o] = make_short4(q[0], q[1], q[2], q[3]);
   } else if (KIND == 1) {
     const int v = min(max(cv_round(res[0]), 0), 255);
     reinterpret_cast<uint8_t*>(dst)[o] = threshold >= 0 ? (uint8_t)(v > threshold) : (uint8_t)v;

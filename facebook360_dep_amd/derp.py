@@ -130,6 +130,8 @@ EXPORTS = [
     "derp_sim_scene_get", "derp_sim_perlin_table", "derp_sim_icosahedron", "derp_sim_noise", "derp_sim_trace_host", "derp_sim_create",
     "derp_sim_destroy", "derp_sim_upload", "derp_sim_render_camera", "derp_sim_render_equirect", "derp_sim_trace_rays",
     "derp_sim_stage_size", "derp_sim_stage",
+    "derp_gc_upload", "derp_gc_download_image", "derp_gc_slices", "derp_gc_set_clean", "derp_gc_sweep", "derp_gc_clean",
+    "derp_gc_run", "derp_gc_result", "derp_gc_stage", "derp_gc_slice_count",
 ]
 
 _lib = None
@@ -585,6 +587,92 @@ class Derp:
                                                   C.c_double(depth), _p(out)))
         return out
 
+    # ---- GeometricConsistency (source/render/GeometricConsistency.cpp): cameras = this context's destinations (the
+    # whole rig, not normalised), rescaled to the small sizes
+    GC_KINDS = {"iffy": 0, "clean": 1, "depth": 2, "final": 3}
+
+    def gc_upload(self, images, small_sizes):
+        """images[cam]: BGRA (or BGR: alpha 65535) u16 [H, W, 4] at full size; small_sizes[cam] = (w, h)."""
+        assert len(images) == self.D and len(small_sizes) == self.D
+        full = []
+        for im in images:
+            im = np.asarray(im, dtype=np.uint16)
+            if im.shape[2] == 3:
+                im = np.concatenate([im, np.full(im.shape[:2] + (1,), 65535, np.uint16)], axis=2)
+            full.append(np.ascontiguousarray(im))
+        self._gc_sizes = [(int(w), int(h)) for w, h in small_sizes]
+        ptrs = (C.c_void_p * self.D)(*[im.ctypes.data for im in full])
+        ints = lambda v: (C.c_int * self.D)(*v)
+        self._ck(lib().derp_gc_upload(self.h, ptrs, ints([im.shape[1] for im in full]), ints([im.shape[0] for im in full]),
+                                      ints([s[0] for s in self._gc_sizes]), ints([s[1] for s in self._gc_sizes])))
+
+    def _gc_shape(self, cam):
+        sizes = getattr(self, "_gc_sizes", [])
+        w, h = sizes[cam] if 0 <= cam < len(sizes) else (1, 1)  # (a bad index is the library's to refuse)
+        return h, w
+
+    def gc_image(self, cam):
+        """the int16 BGRA image of `cam` at its small size: the reference and the texture of the sweep"""
+        out = np.zeros(self._gc_shape(cam) + (4,), dtype=np.int16)
+        self._ck(lib().derp_gc_download_image(self.h, cam, _p(out)))
+        return out
+
+    def gc_slices(self, dst, disparity_step=0.5):
+        """-> the slice disparities of `dst`, f32 [sliceCount]"""
+        n = C.c_int()
+        self._ck(lib().derp_gc_slices(self.h, dst, C.c_double(disparity_step), C.byref(n), None, 0))
+        out = np.zeros(n.value, dtype=np.float32)
+        self._ck(lib().derp_gc_slices(self.h, dst, C.c_double(disparity_step), C.byref(n), _p(out), n.value))
+        return out
+
+    def gc_set_clean(self, clean):
+        """clean[cam] f32 [h, w] at the small sizes, or None"""
+        if clean is None:
+            self._ck(lib().derp_gc_set_clean(self.h, None))
+            return
+        clean = [np.ascontiguousarray(d, dtype=np.float32) for d in clean]
+        assert [d.shape for d in clean] == [self._gc_shape(i) for i in range(self.D)]
+        self._ck(lib().derp_gc_set_clean(self.h, (C.c_void_p * self.D)(*[d.ctypes.data for d in clean])))
+
+    def gc_sweep(self, dst, disparity_step=0.5, use_clean=False, agree_fraction=0.75, split=0):
+        """computeDepth of one destination -> depth f32 [h, w]"""
+        out = np.zeros(self._gc_shape(dst), dtype=np.float32)
+        self._ck(lib().derp_gc_sweep(self.h, dst, C.c_double(disparity_step), int(bool(use_clean)),
+                                     C.c_double(agree_fraction), split, _p(out)))
+        return out
+
+    def gc_clean(self, depths, agree_fraction=0.75):
+        """cleanDepth over any per-camera depth maps f32 [h_i, w_i] -> the cleaned maps"""
+        depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+        assert len(depths) == self.D
+        outs = [np.zeros_like(d) for d in depths]
+        ints = lambda v: (C.c_int * self.D)(*v)
+        self._ck(lib().derp_gc_clean(self.h, (C.c_void_p * self.D)(*[d.ctypes.data for d in depths]),
+                                     ints([d.shape[1] for d in depths]), ints([d.shape[0] for d in depths]),
+                                     C.c_double(agree_fraction), (C.c_void_p * self.D)(*[o.ctypes.data for o in outs])))
+        return outs
+
+    def gc_run(self, disparity_step=0.5, agree_fraction=0.75, pass_count=2, keep_clean=False):
+        """processFrame of the uploaded frame; results through gc_result"""
+        self._ck(lib().derp_gc_run(self.h, C.c_double(disparity_step), C.c_double(agree_fraction), pass_count,
+                                   int(bool(keep_clean))))
+
+    def gc_result(self, kind, cam, pass_index=0):
+        """kind: "iffy", "clean" (of pass), "depth" (of pass), "final" -> f32 [h, w]"""
+        out = np.zeros(self._gc_shape(cam), dtype=np.float32)
+        self._ck(lib().derp_gc_result(self.h, self.GC_KINDS[kind], pass_index, cam, _p(out)))
+        return out
+
+    def gc_stage(self, dst, src, slice_index, disparity_step=0.5, use_clean=False, agree_fraction=0.75):
+        """-> dict(sample, average, average_of_sq: i16 [h, w, 4]; cost: f32 [h, w]) of one (dst, src, slice)"""
+        shape = self._gc_shape(dst)
+        out = {k: np.zeros(shape + (4,), dtype=np.int16) for k in ("sample", "average", "average_of_sq")}
+        out["cost"] = np.zeros(shape, dtype=np.float32)
+        self._ck(lib().derp_gc_stage(self.h, dst, src, slice_index, C.c_double(disparity_step), int(bool(use_clean)),
+                                     C.c_double(agree_fraction), _p(out["sample"]), _p(out["average"]),
+                                     _p(out["average_of_sq"]), _p(out["cost"])))
+        return out
+
     # ---- camera meshes (source/mesh_stream/ConvertToBinary.cpp:150-245): one mesh per context, the one built last
     def mesh_build(self, cam, disparity, resolution=None, depth_scale=1.0, mask=None, tear_ratio=0.95):
         """convertDepth up to applyMaskToVertexesAndFaces: disparity f32 [h, w], optional foreground mask u8 of any
@@ -778,6 +866,17 @@ class Derp:
 
 
 MESH_EXIT_BUDGET, MESH_EXIT_INFINITE_THRESHOLD, MESH_EXIT_STUCK = 0, 1, 2
+
+
+def gc_slice_count(cams, dst, small_size, disparity_step=0.5):
+    """GeometricConsistency's sliceCount for destination `dst` of the rig `cams` (as the file holds it) at its small
+    size (w, h), on the host (no device); raises DerpError with the refusal's text."""
+    a = (CameraDesc * len(cams))(*[camera_desc(c) for c in cams])
+    n = C.c_int()
+    if lib().derp_gc_slice_count(a, len(cams), dst, int(small_size[0]), int(small_size[1]), C.c_double(disparity_step),
+                                 C.byref(n)):
+        raise DerpError(lib().derp_last_error(None).decode())
+    return n.value
 
 
 def mesh_setup_host(vertices, faces, equi_error=True):

@@ -360,6 +360,48 @@ int derp_mesh_simplify_parallel(derp_ctx* ctx, int num_faces_out, float strictne
 int derp_mesh_parallel_pass(derp_ctx* ctx, int pass, derp_mesh_pass* out);
 int derp_mesh_download_f64(derp_ctx* ctx, double* vertices, int32_t* faces);
 int derp_mesh_download(derp_ctx* ctx, int clamp_negative_z, float* vtx, uint32_t* idx);
+/* ---- GeometricConsistency (source/render/GeometricConsistency.cpp): plane-sweep depth with cross-camera cleaning ----
+ * The cameras are the destinations of derp_create (the whole rig passed as both src and dst, not normalised); `cam`,
+ * `dst` and `src` index them. The reference's OpenGL reprojection (ReprojectionGpuUtil.h reproject<T>, :208-214) is
+ * replaced by a defined sampling rule; everything after it is the reference's arithmetic.
+ * derp_gc_upload: loadImages + downscale + computeReference (:158-163, :324-331, :338): per camera one full-size BGRA
+ *   u16 image [full_h][full_w][4] (alpha 65535 where the file has none), area-resized to the small size (at least
+ *   3 x 3, the size Camera::rescale is given) and converted to int16 with 32767 / 65535. The result is both the
+ *   destination's reference and the source's texture. derp_gc_download_image reads one back, [h][w][4].
+ * derp_gc_slices: sliceCount of computeDepth (:186-192) for `dst` and its slice disparities (:126-128; null: the count
+ *   alone). Refuses a rig whose mean camera distance from the origin is 1 m or more, and a count below 1.
+ * derp_gc_slice_count: the same count on the host, with no context and no device, for a rig as the file holds it and
+ *   the destination's small size; a refusal leaves its text in derp_last_error(NULL).
+ * derp_gc_set_clean: the clean depth of every camera [h][w] at the small sizes, for sweeps and stages with use_clean
+ *   (null: none).
+ * derp_gc_sweep: computeDepth + winnerTakesAll (:132-258) of one destination -> depth [h][w], NaN on the outermost
+ *   rows and columns and where no slice has a cost. split: parts the slice range is swept in (grid dimension), 0 = the
+ *   library's choice; the result does not depend on it.
+ * derp_gc_clean: cleanDepth / isPointBad (:260-310) over caller-supplied depth maps of any origin, one [h[i]][w[i]]
+ *   per camera, cameras rescaled to those sizes -> out[i], NaN where another camera's map contradicts the depth. Needs
+ *   no derp_gc_upload.
+ * derp_gc_run: processFrame (:333-384) of the uploaded frame; derp_gc_result reads what the tool dumps: DERP_GC_IFFY
+ *   (<id>_iffy), DERP_GC_CLEAN (<id>_<pass>_clean), DERP_GC_DEPTH (<id>_<pass>), and DERP_GC_FINAL, the depths after
+ *   the last pass (after restoreCleanDepth when keep_clean).
+ * derp_gc_stage: for one (dst, src, slice): the int16 sample image (`image`, :208 + occlusion :212-226), `average` and
+ *   `averageOfSq` (:229-236), each [h][w][4], and the slice's cost plane over all sources (:251). Null outputs are
+ *   skipped. The outermost pixels are computed like the others (the sweep blanks them at the end). */
+enum { DERP_GC_IFFY = 0, DERP_GC_CLEAN = 1, DERP_GC_DEPTH = 2, DERP_GC_FINAL = 3 };
+int derp_gc_upload(derp_ctx* ctx, const uint16_t* const* bgra, const int* full_w, const int* full_h, const int* small_w,
+                   const int* small_h);
+int derp_gc_download_image(derp_ctx* ctx, int cam, int16_t* out_bgra);
+int derp_gc_slices(derp_ctx* ctx, int dst, double disparity_step, int* count, float* disparities, int cap);
+int derp_gc_slice_count(const derp_camera_desc* cams, int n_cams, int dst, int small_w, int small_h,
+                        double disparity_step, int* count);
+int derp_gc_set_clean(derp_ctx* ctx, const float* const* clean);
+int derp_gc_sweep(derp_ctx* ctx, int dst, double disparity_step, int use_clean, double agree_fraction, int split,
+                  float* depth);
+int derp_gc_clean(derp_ctx* ctx, const float* const* depths, const int* w, const int* h, double agree_fraction,
+                  float* const* out);
+int derp_gc_run(derp_ctx* ctx, double disparity_step, double agree_fraction, int pass_count, int keep_clean);
+int derp_gc_result(derp_ctx* ctx, int kind, int pass, int cam, float* out);
+int derp_gc_stage(derp_ctx* ctx, int dst, int src, int slice, double disparity_step, int use_clean,
+                  double agree_fraction, int16_t* sample, int16_t* average, int16_t* average_of_sq, float* cost);
 /* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
  * range, a negative budget, more than 2^31 - 1 vertices or faces).
  * derp_mesh_setup_host: computeInitialQuadrics over plain arrays: vertices f64 [nv][3], faces i32 [nf][3] -> the three
