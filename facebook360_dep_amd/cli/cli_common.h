@@ -120,6 +120,7 @@ struct Flags {
   void str(const std::string& n, const std::string& d, const std::string& h) { def("string", n, d, h); }
   void i32(const std::string& n, int d, const std::string& h) { def("int32", n, std::to_string(d), h); }
   void u32(const std::string& n, unsigned d, const std::string& h) { def("uint32", n, std::to_string(d), h); }
+  void u64(const std::string& n, unsigned long long d, const std::string& h) { def("uint64", n, std::to_string(d), h); }
   void dbl(const std::string& n, double d, const std::string& h) {
     std::ostringstream ss;
     ss.precision(17);
@@ -131,6 +132,7 @@ struct Flags {
   std::string s(const std::string& n) const { return defs.at(n).value; }
   static int int_base(const std::string& v) { return v.size() > 1 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X') ? 16 : 10; }
   unsigned u(const std::string& n) const { return (unsigned)strtoull(defs.at(n).value.c_str(), nullptr, int_base(defs.at(n).value)); }
+  unsigned long long ull(const std::string& n) const { return strtoull(defs.at(n).value.c_str(), nullptr, int_base(defs.at(n).value)); }
   int i(const std::string& n) const { return (int)strtoll(defs.at(n).value.c_str(), nullptr, int_base(defs.at(n).value)); }
   double d(const std::string& n) const { return atof(defs.at(n).value.c_str()); }
   bool b(const std::string& n) const {
@@ -148,9 +150,15 @@ struct Flags {
       fprintf(stderr, "ERROR: unknown command line flag '%s'\n", name.c_str());
       exit(1);
     }
-    if (it->second.type == "int32" || it->second.type == "uint32" || it->second.type == "double") {
+    if (it->second.type == "int32" || it->second.type == "uint32" || it->second.type == "uint64" || it->second.type == "double") {
       char* end = nullptr;
-      if (it->second.type == "uint32") {  // gflags: no sign, 32-bit range
+      if (it->second.type == "uint64") {  // gflags: no sign, 64-bit range
+        errno = 0;
+        strtoull(value.c_str(), &end, int_base(value));
+        if (errno == ERANGE || value.find('-') != std::string::npos) {
+          end = nullptr;
+        }
+      } else if (it->second.type == "uint32") {  // gflags: no sign, 32-bit range
         errno = 0;
         const unsigned long long v = strtoull(value.c_str(), &end, int_base(value));
         if (errno == ERANGE || v > UINT32_MAX || value.find('-') != std::string::npos) {

@@ -132,6 +132,8 @@ EXPORTS = [
     "derp_sim_stage_size", "derp_sim_stage",
     "derp_gc_upload", "derp_gc_download_image", "derp_gc_slices", "derp_gc_set_clean", "derp_gc_sweep", "derp_gc_clean",
     "derp_gc_run", "derp_gc_result", "derp_gc_stage", "derp_gc_slice_count",
+    "derp_sweep_upload", "derp_sweep_overlaps", "derp_sweep_equirect_bounds", "derp_sweep_equirect",
+    "derp_sweep_overlap_disparities", "derp_sweep_equirect_depths", "derp_sweep_crop_size", "derp_rig_center",
 ]
 
 _lib = None
@@ -859,6 +861,47 @@ class Derp:
         self._ck(lib().derp_device_memory(self.h, C.byref(f), C.byref(t)))
         return f.value, t.value
 
+    # ---- the rig preview tools: GenerateCameraOverlaps / GenerateEquirect
+    def sweep_upload(self, images, resolutions):
+        """images: per camera float BGRA [h, w, 4] at its scaled size; resolutions: per camera (x, y) the camera is
+        rescaled to (doubles: resolution * scale, not rounded)"""
+        assert len(images) == self.D and len(resolutions) == self.D
+        ims = [np.ascontiguousarray(im, dtype=np.float32) for im in images]
+        assert all(im.ndim == 3 and im.shape[2] == 4 for im in ims)
+        ints = lambda v: (C.c_int * self.D)(*[int(x) for x in v])  # noqa: E731
+        res = np.ascontiguousarray(np.asarray(resolutions, dtype=np.float64).reshape(self.D, 2))
+        ptrs = (C.c_void_p * self.D)(*[im.ctypes.data for im in ims])
+        self._ck(lib().derp_sweep_upload(self.h, ptrs, ints([im.shape[1] for im in ims]), ints([im.shape[0] for im in ims]),
+                                         _p(res)))
+        self._sweep_shapes = [im.shape[:2] for im in ims]
+
+    def sweep_overlaps(self, dst, disparities, u8=False):
+        """-> [n, h, w, 4] float32 (NaN where no camera sees the point) or uint8 (255.0f * image)"""
+        d = np.ascontiguousarray(disparities, dtype=np.float32).reshape(-1)
+        shapes = getattr(self, "_sweep_shapes", [])
+        if not 0 <= dst < len(shapes):
+            raise DerpError("sweep_upload has not been called, or bad camera index %d" % dst)
+        out = np.zeros((len(d),) + tuple(shapes[dst]) + (4,), dtype=np.uint8 if u8 else np.float32)
+        self._ck(lib().derp_sweep_overlaps(self.h, dst, _p(d), len(d), int(bool(u8)), _p(out)))
+        return out
+
+    def sweep_equirect_bounds(self, width, height, depth):
+        """-> (minX, maxX, minY, maxY) of the columns and rows at which any camera sees the equirect's point"""
+        b = (C.c_int * 4)()
+        self._ck(lib().derp_sweep_equirect_bounds(self.h, int(width), int(height), C.c_float(depth), b))
+        return tuple(b)
+
+    def sweep_equirect(self, width, height, depths, window=None, out_size=None, black_bg=False, u8=False):
+        """window: None or (minX, maxX, minY, maxY) with out_size = (w, h) -> [n, h, w, 4] float32 or uint8"""
+        d = np.ascontiguousarray(depths, dtype=np.float32).reshape(-1)
+        ow, oh = (width, height) if out_size is None else out_size
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        bg = (C.c_float * 4)(0, 0, 0 if black_bg else 1, 1)
+        out = np.zeros((len(d), int(oh), int(ow), 4), dtype=np.uint8 if u8 else np.float32)
+        self._ck(lib().derp_sweep_equirect(self.h, int(width), int(height), win, int(ow), int(oh), _p(d), len(d), bg,
+                                           int(bool(u8)), _p(out)))
+        return out
+
     def device_name(self):
         buf = C.create_string_buffer(256)
         self._ck(lib().derp_device_name(self.h, buf, 256))
@@ -877,6 +920,47 @@ def gc_slice_count(cams, dst, small_size, disparity_step=0.5):
                                  C.byref(n)):
         raise DerpError(lib().derp_last_error(None).decode())
     return n.value
+
+
+def _host_ck(rc):
+    if rc:
+        raise DerpError(lib().derp_last_error(None).decode())
+
+
+def sweep_overlap_disparities(num_depths, min_depth_m=1, max_depth_m=10):
+    """GenerateCameraOverlaps' disparities in sweep order and their files' stems (int(depth * 100)), on the host"""
+    d, s = np.zeros(max(num_depths, 0), dtype=np.float32), np.zeros(max(num_depths, 0), dtype=np.int32)
+    _host_ck(lib().derp_sweep_overlap_disparities(int(num_depths), C.c_uint64(min_depth_m), C.c_uint64(max_depth_m), _p(d), _p(s)))
+    return d, s
+
+
+def sweep_equirect_depths(num_depths, depth_min=1.0, depth_max=10.0):
+    """GenerateEquirect's depths by index and their files' stems, on the host"""
+    d, s = np.zeros(max(num_depths, 0), dtype=np.float32), np.zeros(max(num_depths, 0), dtype=np.int32)
+    _host_ck(lib().derp_sweep_equirect_depths(int(num_depths), C.c_double(depth_min), C.c_double(depth_max), _p(d), _p(s)))
+    return d, s
+
+
+def sweep_crop_size(height, bounds):
+    """--crop_equirect's width for the bounds (minX, maxX, minY, maxY); raises DerpError on an empty box"""
+    w = C.c_int()
+    _host_ck(lib().derp_sweep_crop_size(int(height), (C.c_int * 4)(*[int(v) for v in bounds]), C.byref(w)))
+    return w.value
+
+
+def rig_center(cams, index):
+    """GenerateEquirect --camera_id: the rig rotated so that camera `index` faces the equirect's centre, on the host.
+    -> the cameras (dicts) with origin, forward, up and right replaced"""
+    a = (CameraDesc * len(cams))(*[camera_desc(c) for c in cams])
+    b = (CameraDesc * len(cams))()
+    _host_ck(lib().derp_rig_center(a, len(cams), int(index), b))
+    out = []
+    for cam, j in zip(cams, b):
+        cam = dict(cam)
+        for k in ("origin", "forward", "up", "right"):
+            cam[k] = [float(v) for v in getattr(j, k)]
+        out.append(cam)
+    return out
 
 
 def mesh_setup_host(vertices, faces, equi_error=True):

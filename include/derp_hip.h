@@ -402,6 +402,39 @@ int derp_gc_run(derp_ctx* ctx, double disparity_step, double agree_fraction, int
 int derp_gc_result(derp_ctx* ctx, int kind, int pass, int cam, float* out);
 int derp_gc_stage(derp_ctx* ctx, int dst, int src, int slice, double disparity_step, int use_clean,
                   double agree_fraction, int16_t* sample, int16_t* average, int16_t* average_of_sq, float* cost);
+/* ---- The rig preview tools (source/render/GenerateCameraOverlaps.cpp, GenerateEquirect.cpp): every camera projected
+ * into a destination camera, or into one equirect of the whole rig, over a series of depths ----
+ * The cameras are the destinations of derp_create (the whole rig, not normalised), as in the conversion group.
+ * derp_sweep_upload: loadScaledImages<cv::Vec4f> + Camera::rescale(resolution * scale) (GenerateCameraOverlaps.cpp:135-145,
+ *   GenerateEquirect.cpp:251-259): per camera one float BGRA image [img_h][img_w][4] at its scaled size (alpha 1 where the
+ *   file has none) and the camera's resolution {x, y} as doubles, which need not be whole or equal the image's size.
+ * derp_sweep_overlaps: projectSrcsToDst (GenerateCameraOverlaps.cpp:54-83) of destination `dst` for each of `n`
+ *   disparities -> out [n][img_h][img_w][4], float (DERP_SWEEP_FLOAT; NaN where no camera sees the point) or the 8-bit
+ *   values of `255.0f * image` (DERP_SWEEP_U8; NaN -> 0).
+ * derp_sweep_equirect_bounds: createCroppedEquirect's first loop (GenerateEquirect.cpp:139-156) over the W x H equirect
+ *   at `depth` -> bounds = {minX, maxX, minY, maxY}; {W, 0, H, 0} where no camera sees anything.
+ * derp_sweep_equirect: createEquirect / createCroppedEquirect + getPixelColor (GenerateEquirect.cpp:79-175) for each of
+ *   `n` depths -> out [n][out_h][out_w][4]. window NULL: the whole equirect (out_w = W, out_h = H); otherwise the four
+ *   bounds, sampled at x * (maxX - minX) / out_w + minX and likewise in y. background_bgra: where no camera sees the point.
+ * Host only, no context and no device; a refusal leaves its text in derp_last_error(NULL):
+ * derp_sweep_overlap_disparities: probeDisparity (ImageUtil.cpp:100-107) of dumpOverlaps
+ *   (GenerateCameraOverlaps.cpp:100-120) and the files' stems int(depth * 100) (stems may be NULL). One depth: the
+ *   farthest (the reference divides 0 by 0).
+ * derp_sweep_equirect_depths: the depth of index i of GenerateEquirect.cpp:264-272 and its stem (saveImage, :74-75).
+ * derp_sweep_crop_size: newWidth of GenerateEquirect.cpp:158-159; refuses an empty box (the reference divides by zero).
+ * derp_rig_center: centerRig (GenerateEquirect.cpp:177-231, transformRig of source/rig/RigTransform.h:73-97) for the
+ *   camera `index` -> out_cams[n], with forward / up / right re-unitarised as Camera::setRotation leaves them. */
+enum { DERP_SWEEP_FLOAT = 0, DERP_SWEEP_U8 = 1 };
+int derp_sweep_upload(derp_ctx* ctx, const float* const* bgra, const int* img_w, const int* img_h, const double* cam_res_xy);
+int derp_sweep_overlaps(derp_ctx* ctx, int dst, const float* disparities, int n, int out_kind, void* out);
+int derp_sweep_equirect_bounds(derp_ctx* ctx, int W, int H, float depth, int* bounds);
+int derp_sweep_equirect(derp_ctx* ctx, int W, int H, const int* window, int out_w, int out_h, const float* depths, int n,
+                        const float* background_bgra, int out_kind, void* out);
+int derp_sweep_overlap_disparities(int num_depths, uint64_t min_depth_m, uint64_t max_depth_m, float* disparities,
+                                   int* stems);
+int derp_sweep_equirect_depths(int num_depths, double depth_min, double depth_max, float* depths, int* stems);
+int derp_sweep_crop_size(int height, const int* bounds, int* new_width);
+int derp_rig_center(const derp_camera_desc* cams, int n, int index, derp_camera_desc* out_cams);
 /* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
  * range, a negative budget, more than 2^31 - 1 vertices or faces).
  * derp_mesh_setup_host: computeInitialQuadrics over plain arrays: vertices f64 [nv][3], faces i32 [nf][3] -> the three
