@@ -447,7 +447,8 @@ int build_color_tables(derp_ctx* c, int dst0, int nd) {
   // a frame that finds the tables of this level as an earlier frame left them (same warps: a sequence running the
   // level frame after frame) skips the tiles no source pixel maps into — they still hold their zeros
   const int skipBlank = c->w.colorTablesCleanLevel == L && nd == c->D && !c->noBlankSkip;
-  hipLaunchKernelGGL(k_reproject_bias, grid, dim3(256), 0, c->stream, V, c->projWarpInv.as<float2>(),
+  const auto kernel = c->reprojectSerial ? k_reproject_bias : k_reproject_bias_front;  // the same tables either way
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, V, c->projWarpInv.as<float2>(),
                      c->w.projColor.as<ushort4>(), c->w.projBias.as<ushort4>(), c->w.projColorT.as<ushort4>(),
                      c->w.tileSeen.as<uint8_t>(), skipBlank);
   KCHECK(c);
@@ -663,6 +664,14 @@ constexpr size_t kBilateralMaxLds = 64 * 1024 - 256;
 bool bilateral_fast_tap_ok(float sigma, float w0, float w1, float w2) {
   const float denom = 2.0f * (sigma * sigma);
   return w1 == 1.0f && w2 == 1.0f && w0 >= 0.0f && std::isfinite(w0) && denom > 0.0f && std::isfinite(denom);
+}
+
+// The preconditions of k_temporal_tiled's FAST form (temporal_tap<true>): all three weights in [0, inf), and
+// 0 < sigma^2 < inf as the kernel computes it
+bool temporal_fast_tap_ok(float sigma, float w0, float w1, float w2) {
+  const float sig2 = sigma * sigma;
+  const auto weight_ok = [](float w) { return w >= 0.0f && std::isfinite(w); };
+  return weight_ok(w0) && weight_ok(w1) && weight_ok(w2) && sig2 > 0.0f && std::isfinite(sig2);
 }
 
 // the tiled kernel with a u16 guide, in the form its parameters allow: the same bits either way
@@ -1037,8 +1046,11 @@ int temporal_launch(derp_ctx* c, const void* const* guides, const float* const* 
     // taps staged through LDS unless the halo makes the tile too big (two buffers of (32 + 2r) x (8 + 2r) x 9 bytes)
     const size_t lds = 2 * ((((size_t)(32 + 2 * radius) * (8 + 2 * radius) * 9) + 15) & ~(size_t)15);
     if (radius >= 0 && lds <= 48 * 1024 && !c->noTemporalTile) {
-      hipLaunchKernelGGL(k_temporal_tiled, grid2d(W, H, planes, kBlk2d), kBlk2d, lds, c->stream, F, W, H, sigma, radius, w0,
-                         w1, w2, out, dst2src);
+      // the form the parameters allow: the same bits either way
+      const bool fast = temporal_fast_tap_ok(sigma, w0, w1, w2) && !c->temporalGeneric;
+      const auto kernel = !fast ? k_temporal_tiled<-1, false> : radius == 1 ? k_temporal_tiled<1, true> : k_temporal_tiled<-1, true>;
+      hipLaunchKernelGGL(kernel, grid2d(W, H, planes, kBlk2d), kBlk2d, lds, c->stream, F, W, H, sigma, radius, w0, w1, w2, out,
+                         dst2src);
     } else {
       hipLaunchKernelGGL(k_temporal, grid2d(W, H, planes, kBlk2d), kBlk2d, 0, c->stream, F, W, H, sigma, radius, w0, w1, w2,
                          out, dst2src);
@@ -1110,6 +1122,12 @@ int derp_create(derp_ctx** out, int device, const derp_camera_desc* src, int n_s
   }
   c->noTemporalTile = getenv("DERP_NO_TEMPORAL_TILE") != nullptr;
   c->noBlankSkip = getenv("DERP_NO_BLANK_SKIP") != nullptr;
+  if (const char* e = getenv("DERP_TEMPORAL_GENERIC")) {
+    c->temporalGeneric = atoi(e) != 0;
+  }
+  if (const char* e = getenv("DERP_REPROJECT_SERIAL")) {
+    c->reprojectSerial = atoi(e) != 0;
+  }
   c->S = n_src;
   c->D = n_dst;
   c->frames.resize(1);

@@ -165,6 +165,10 @@ struct derp_ctx {
   size_t ldsPerCu = 160 * 1024;  // hipDeviceProp.maxSharedMemoryPerMultiProcessor (derp_create)
   bool noTemporalTile = false;  // DERP_NO_TEMPORAL_TILE (developer A/B: the direct form of the temporal filter)
   bool noBlankSkip = false;     // DERP_NO_BLANK_SKIP (developer A/B: every frame rewrites the blank tiles of the colour tables)
+  // DERP_TEMPORAL_GENERIC (developer A/B: k_temporal_tiled's generic form — full expf, a mask read per tap, run-time
+  // radius — where the fast form would run) and DERP_REPROJECT_SERIAL (developer A/B: k_reproject_bias's one-cell-at-a-time
+  // form instead of the front-loaded one); same results either way, read once in derp_create
+  bool temporalGeneric = false, reprojectSerial = false;
   // ---- the tool families' states
   std::unique_ptr<SmrState> smr;
   std::unique_ptr<RephotoState> rephoto;

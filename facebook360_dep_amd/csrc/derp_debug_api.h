@@ -135,6 +135,23 @@ int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
     }
     return 0;
   }
+  if (which == 6 || which == 7) {  // the whole padded plane, ring included: what the cost kernels read at the image edge
+    const size_t plane = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC);
+    const DevBuf& buf = which == 6 ? c->w.projColor : c->w.projBias;
+    if (buf.bytes < (tab + 1) * plane * sizeof(ushort4)) {
+      return fail(c, "the colour tables of this level have not been built");
+    }
+    HIPCHK(c, hipMemcpy(out, buf.as<ushort4>() + tab * plane, plane * sizeof(ushort4), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (which == 8) {  // k_reproject_bias's tileSeen flags of the table, [tilesY][tilesX]
+    const size_t tiles = (size_t)((W + kRbTile - 1) / kRbTile) * ((H + kRbTile - 1) / kRbTile);
+    if (c->w.tileSeen.bytes < (tab + 1) * tiles) {
+      return fail(c, "the colour tables of this level have not been built");
+    }
+    HIPCHK(c, hipMemcpy(out, c->w.tileSeen.as<uint8_t>() + tab * tiles, tiles, hipMemcpyDeviceToHost));
+    return 0;
+  }
   return fail(c, "unknown table id %d", which);
 }
 

@@ -1281,37 +1281,65 @@ __device__ __forceinline__ int cv_round(float v) {
 
 // cv::remap(src, map, INTER_CUBIC, BORDER_CONSTANT 0) at ONE map coordinate (mx, my) of a CV_16UC3 image
 // (DerpUtil.cpp:199-205): 1/32-px fixed point, 4x4 taps, float weights, saturate_cast<ushort> = round-half-even.
+// the 4 x 4 taps of an interior position, each tap row as two 16-byte words (four BGRX u16 texels)
+struct CubicTaps {
+  u4a8 a[4], b[4];
+};
+// The interior sum of remap_cubic_u16: per channel, each tap row summed left to right, then the four rows top to bottom
+// (fx, fy: the 1/32-px fractions).
+__device__ __forceinline__ void cubic_rows_sum(const CubicTaps& t, const float* cx, const float* cy, float* sum) {
+  float rowsum[4][3];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u4a8 a = t.a[i], b = t.b[i];
+    const float w0 = cy[i] * cx[0], w1 = cy[i] * cx[1], w2 = cy[i] * cx[2], w3 = cy[i] * cx[3];
+    rowsum[i][0] = (float)(a.x & 0xffff) * w0 + (float)(a.z & 0xffff) * w1 + (float)(b.x & 0xffff) * w2 + (float)(b.z & 0xffff) * w3;
+    rowsum[i][1] = (float)(a.x >> 16) * w0 + (float)(a.z >> 16) * w1 + (float)(b.x >> 16) * w2 + (float)(b.z >> 16) * w3;
+    rowsum[i][2] = (float)(a.y & 0xffff) * w0 + (float)(a.w & 0xffff) * w1 + (float)(b.y & 0xffff) * w2 + (float)(b.w & 0xffff) * w3;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float acc = rowsum[0][c];
+    acc += rowsum[1][c];
+    acc += rowsum[2][c];
+    acc += rowsum[3][c];
+    sum[c] = acc;
+  }
+}
+__device__ __forceinline__ void cubic_interior_sum(const CubicTaps& t, int fx, int fy, float* sum) {
+  float cx[4], cy[4];
+  cubic_coeffs((float)fx * (1.f / 32), cx);
+  cubic_coeffs((float)fy * (1.f / 32), cy);
+  cubic_rows_sum(t, cx, cy, sum);
+}
+// saturate_cast<ushort> of the three channel sums
+__device__ __forceinline__ ushort4 cubic_saturate_u16(const float* sum) {
+  const int r0 = min(max(cv_round(sum[0]), 0), 65535), r1 = min(max(cv_round(sum[1]), 0), 65535),
+            r2 = min(max(cv_round(sum[2]), 0), 65535);
+  return make_ushort4((unsigned short)r0, (unsigned short)r1, (unsigned short)r2, 0);
+}
+
 __device__ __forceinline__ ushort4 remap_cubic_u16(const ushort4* __restrict__ img, int W, int H, float mx, float my) {
   const int fsx = cv_round(mx * 32.0f), fsy = cv_round(my * 32.0f);
   const int fx = fsx & 31, fy = fsy & 31;
   const int sx = min(max(fsx >> 5, -32768), 32767) - 1, sy = min(max(fsy >> 5, -32768), 32767) - 1;
-  float cx[4], cy[4];
-  cubic_coeffs((float)fx * (1.f / 32), cx);
-  cubic_coeffs((float)fy * (1.f / 32), cy);
   float sum[3];
   if ((unsigned)sx < (unsigned)max(W - 3, 0) && (unsigned)sy < (unsigned)max(H - 3, 0)) {
-    float rowsum[4][3];
+    CubicTaps t;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // the four texels of a tap row as two 16-byte loads (8-byte aligned)
       const u4a8* r = reinterpret_cast<const u4a8*>(img + (size_t)(sy + i) * W + sx);
-      const u4a8 a = r[0], b = r[1];
-      const float w0 = cy[i] * cx[0], w1 = cy[i] * cx[1], w2 = cy[i] * cx[2], w3 = cy[i] * cx[3];
-      rowsum[i][0] = (float)(a.x & 0xffff) * w0 + (float)(a.z & 0xffff) * w1 + (float)(b.x & 0xffff) * w2 + (float)(b.z & 0xffff) * w3;
-      rowsum[i][1] = (float)(a.x >> 16) * w0 + (float)(a.z >> 16) * w1 + (float)(b.x >> 16) * w2 + (float)(b.z >> 16) * w3;
-      rowsum[i][2] = (float)(a.y & 0xffff) * w0 + (float)(a.w & 0xffff) * w1 + (float)(b.y & 0xffff) * w2 + (float)(b.w & 0xffff) * w3;
+      t.a[i] = r[0];
+      t.b[i] = r[1];
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float acc = rowsum[0][c];
-      acc += rowsum[1][c];
-      acc += rowsum[2][c];
-      acc += rowsum[3][c];
-      sum[c] = acc;
-    }
+    cubic_interior_sum(t, fx, fy, sum);
   } else if (sx >= W || sx + 4 <= 0 || sy >= H || sy + 4 <= 0) {
     sum[0] = sum[1] = sum[2] = 0.f;
   } else {
+    float cx[4], cy[4];
+    cubic_coeffs((float)fx * (1.f / 32), cx);
+    cubic_coeffs((float)fy * (1.f / 32), cy);
     sum[0] = sum[1] = sum[2] = 0.f;
     for (int i = 0; i < 4; ++i) {
       const int yy = sy + i;
@@ -1331,9 +1359,7 @@ __device__ __forceinline__ ushort4 remap_cubic_u16(const ushort4* __restrict__ i
       }
     }
   }
-  const int r0 = min(max(cv_round(sum[0]), 0), 65535), r1 = min(max(cv_round(sum[1]), 0), 65535),
-            r2 = min(max(cv_round(sum[2]), 0), 65535);
-  return make_ushort4((unsigned short)r0, (unsigned short)r1, (unsigned short)r2, 0);
+  return cubic_saturate_u16(sum);
 }
 
 // projWarpInv(d, s) = computeWarpDstToSrc(camDst d, camSrc s) and projWarp(d', s') = computeWarpDstToSrc(camSrc s',
@@ -1498,6 +1524,205 @@ __global__ void __launch_bounds__(256)
         pb[(size_t)oy * OW + ox] = bia;
         if (pt) {
           pt[tiled_index(tilesX, ox, oy)] = col;
+        }
+      }
+    }
+  }
+}
+
+// reflect101 for p in [-1, len]: one step of its loop at the most
+__device__ __forceinline__ int reflect101_near(int p, int len) {
+  return len == 1 ? 0 : p < 0 ? -p : p >= len ? 2 * len - 2 - p : p;
+}
+// what a cell of the 34 x 34 tile takes (k_reproject_bias_front)
+enum : unsigned {
+  kRbZero = 0,      // NaN map, or every tap outside the source: the constant border 0
+  kRbInterior = 1,  // all 16 taps inside: eight 16-byte loads from a 32-bit offset
+  kRbBorder = 2,    // taps straddle the source edge: remap_cubic_u16's tap-by-tap form
+  kRbNone = 3       // no cell (past the tile, or a halo position the image's reflected ring does not reach)
+};
+constexpr int kRbTrips = (kRbCells + 255) / 256;
+
+// k_reproject_bias with its maps front-loaded (the default; DERP_REPROJECT_SERIAL=1 runs the form above, same tables bit
+// for bit). The form above walks its cells one at a time: map load, then gathers, then arithmetic, five times over, each
+// load behind the branches of the cell before it. Here a thread
+//   1. reads the maps of all its cells first, at clamped coordinates (unconditional loads), and derives once per cell
+//      what it takes (kRb*), the 1/32-px fractions and the 32-bit byte offset of its first tap from the source plane:
+//      one map latency per block instead of five;
+//   2. per cell, gathers and sums when a ballot says some lane of the wave has an interior cell (lanes without one read
+//      the plane's origin: in bounds, since an interior cell exists only from 4 x 4 up), and runs the tap-by-tap border
+//      form when a ballot says some lane needs it (it reads its map again: rare);
+//   3. takes the cubic coefficients of the 32 possible fractions from an LDS table that the block fills at its start with
+//      the expression remap_cubic_u16 evaluates per position (44 of its ~316 VALU instructions per cell; ~218 here).
+// Cells are numbered as above (k = tid + 256 i, row-major over the 34-wide tile); (tx, ty) advance by (18, 7) per trip
+// instead of a division. Phase 2 is the same sums and stores, with (s + 4) / 9 as trunc((s + 4) * fl(1/9)) (equal for
+// every sum of nine u16: tests/test_abi.py) and the ring loops only in blocks that touch the image edge.
+// Six waves per SIMD (80 VGPRs, no scratch): measured against five (94, what the allocator takes unasked) and against
+// seven and eight (which spill in the gather); issuing cell i + 1's gathers ahead of cell i's arithmetic was measured
+// too and lost to the registers it holds (profiles/r15_tables_temporal.txt).
+__global__ void __launch_bounds__(256, 6)
+    k_reproject_bias_front(LevelView V, const float2* __restrict__ warpInv, ushort4* __restrict__ projColor,
+                           ushort4* __restrict__ projBias, ushort4* __restrict__ projColorT, uint8_t* __restrict__ tileSeen,
+                           int skipBlank) {
+  __shared__ ushort4 tile[kRbCells];
+  __shared__ float4 coefTab[32];  // cubic_coeffs of the 32 possible 1/32-px fractions
+  const int tab = blockIdx.z;  // dl * (S - 1) + slot
+  uint8_t* seen = tileSeen + ((size_t)tab * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (skipBlank && !*seen) {
+    return;
+  }
+  if (threadIdx.x < 32) {
+    float c[4];
+    cubic_coeffs((float)(int)threadIdx.x * (1.f / 32), c);  // the expression remap_cubic_u16 evaluates per position
+    coefTab[threadIdx.x] = make_float4(c[0], c[1], c[2], c[3]);
+  }
+  const int dl = tab / (V.S - 1), sl = tab - dl * (V.S - 1);
+  const int own = V.dst2src[V.dst0 + dl];
+  const int s = sl < own ? sl : sl + 1;
+  const int x0 = blockIdx.x * kRbTile, y0 = blockIdx.y * kRbTile;
+  const int W = V.W, H = V.H;
+  const int OW = W + 2 * kPadC, OH = H + 2 * kPadC;
+  const size_t plane = (size_t)OW * OH, n = (size_t)W * H;
+  const ushort4* img = V.srcColor + (size_t)s * n;
+  const float2* map = warpInv + (size_t)tab * n;
+  int mapPitch = W;
+  const int ds = batch_dst_of_source(V, s);
+  if (ds >= 0) {
+    mapPitch = W + 2 * kPadW;
+    map = V.projWarp + ((size_t)ds * (V.S - 1) + slot(own, s)) * warp_plane(V) + (size_t)kPadW * mapPitch + kPadW;
+  }
+  const int tid = threadIdx.x;
+  // ---- phase 1a: the maps of this thread's cells
+  float2 m[kRbTrips];
+  bool cell[kRbTrips];
+  {
+    int ty = tid / kRbPitch, tx = tid - ty * kRbPitch;
+#pragma unroll
+    for (int i = 0; i < kRbTrips; ++i) {
+      const int qx = x0 - 1 + tx, qy = y0 - 1 + ty;
+      cell[i] = tid + 256 * i < kRbCells && qx <= W && qy <= H;  // (qx, qy >= -1 always)
+      const int rx = reflect101_near(min(qx, W), W), ry = reflect101_near(min(qy, H), H);
+      m[i] = at32(map, (unsigned)(ry * mapPitch + rx));
+      tx += 256 % kRbPitch;
+      ty += 256 / kRbPitch;
+      if (tx >= kRbPitch) {
+        tx -= kRbPitch;
+        ++ty;
+      }
+    }
+  }
+  // ---- phase 1b: what each cell takes
+  unsigned off[kRbTrips], st[kRbTrips];  // st: fx | fy << 5 | kRb* << 10
+  int any = 0;
+#pragma unroll
+  for (int i = 0; i < kRbTrips; ++i) {
+    // as remap_cubic_u16 derives them
+    const int fsx = cv_round(m[i].x * 32.0f), fsy = cv_round(m[i].y * 32.0f);
+    const int sx = min(max(fsx >> 5, -32768), 32767) - 1, sy = min(max(fsy >> 5, -32768), 32767) - 1;
+    // NaN map -> (-32768, -32768) in cv::remap's fixed point -> every tap outside -> constant border 0
+    const bool valid = cell[i] && !(m[i].x != m[i].x);
+    any |= valid;
+    const bool interior = valid && (unsigned)sx < (unsigned)max(W - 3, 0) && (unsigned)sy < (unsigned)max(H - 3, 0);
+    const bool outside = sx >= W || sx + 4 <= 0 || sy >= H || sy + 4 <= 0;
+    const unsigned kind = !cell[i] ? kRbNone : interior ? kRbInterior : (!valid || outside) ? kRbZero : kRbBorder;
+    off[i] = interior ? (unsigned)(sy * W + sx) * 8u : 0u;
+    st[i] = (unsigned)(fsx & 31) | (unsigned)(fsy & 31) << 5 | kind << 10;
+  }
+  __syncthreads();  // coefTab (the map loads above are in flight across it)
+  // ---- phase 1c: gather and sum, cell by cell
+  const unsigned rowBytes = (unsigned)W * 8u;
+  const char* imgB = reinterpret_cast<const char*>(img);
+#pragma unroll
+  for (int i = 0; i < kRbTrips; ++i) {
+    const unsigned kind = st[i] >> 10;
+    ushort4 res = make_ushort4(0, 0, 0, 0);
+    if (__ballot(kind == kRbInterior) != 0) {  // (wave-uniform)
+      CubicTaps t;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        t.a[r] = *reinterpret_cast<const u4a8*>(imgB + (off[i] + (unsigned)r * rowBytes));
+        t.b[r] = *reinterpret_cast<const u4a8*>(imgB + (off[i] + (unsigned)r * rowBytes + 16u));
+      }
+      const float4 tx4 = coefTab[st[i] & 31], ty4 = coefTab[st[i] >> 5 & 31];
+      const float cx[4] = {tx4.x, tx4.y, tx4.z, tx4.w}, cy[4] = {ty4.x, ty4.y, ty4.z, ty4.w};
+      float sum[3];
+      cubic_rows_sum(t, cx, cy, sum);
+      const ushort4 r = cubic_saturate_u16(sum);
+      if (kind == kRbInterior) {
+        res = r;
+      }
+    }
+    if (__ballot(kind == kRbBorder) != 0) {  // (wave-uniform)
+      if (kind == kRbBorder) {
+        const int k = tid + 256 * i;
+        const int ty = k / kRbPitch, tx = k - ty * kRbPitch;
+        const int rx = reflect101_near(x0 - 1 + tx, W), ry = reflect101_near(y0 - 1 + ty, H);
+        const float2 mb = at32(map, (unsigned)(ry * mapPitch + rx));
+        res = remap_cubic_u16(img, W, H, mb.x, mb.y);
+      }
+    }
+    if (kind != kRbNone) {
+      tile[tid + 256 * i] = res;
+    }
+  }
+  any = __syncthreads_or(any);
+  if (!skipBlank && threadIdx.x == 0) {
+    *seen = (uint8_t)(any != 0);
+  }
+  // ---- phase 2: colours, their 3x3 boxes, and the ring
+  ushort4* pc = projColor + (size_t)tab * plane;
+  ushort4* pb = projBias + (size_t)tab * plane;
+  const int tilesX = tiled_tiles_x(W);
+  ushort4* pt = projColorT ? projColorT + (size_t)tab * tiled_plane(W, H) : nullptr;
+  const int lx = tid & 31;
+  const int x = x0 + lx;
+  if (x >= W) {
+    return;
+  }
+  // (block-uniform) only a block that touches the image edge has pixels with ring texels to replicate into
+  const bool edge = x0 == 0 || y0 == 0 || x0 + kRbTile >= W || y0 + kRbTile >= H;
+  const int oxa = x == 0 ? 0 : x + kPadC, oxb = x == W - 1 ? OW - 1 : x + kPadC;
+#pragma unroll
+  for (int j = 0; j < kRbTile / 8; ++j) {
+    const int ly = (tid >> 5) + 8 * j;
+    const int y = y0 + ly;
+    if (y >= H) {
+      break;
+    }
+    const ushort4* t = &tile[(ly + 1) * kRbPitch + lx + 1];
+    unsigned s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll
+    for (int v = -1; v <= 1; ++v) {
+#pragma unroll
+      for (int u = -1; u <= 1; ++u) {
+        const ushort4 q = t[v * kRbPitch + u];
+        s0 += q.x;
+        s1 += q.y;
+        s2 += q.z;
+      }
+    }
+    const ushort4 col = t[0];
+    const float ninth = 1.0f / 9.0f;
+    const ushort4 bia = make_ushort4((unsigned short)(int)((float)(s0 + 4) * ninth), (unsigned short)(int)((float)(s1 + 4) * ninth),
+                                     (unsigned short)(int)((float)(s2 + 4) * ninth), 0);
+    if (!edge) {
+      const unsigned o = (unsigned)((y + kPadC) * OW + x + kPadC);
+      at32(pc, o) = col;
+      at32(pb, o) = bia;
+      if (pt) {
+        at32(pt, (unsigned)tiled_index(tilesX, x + kPadC, y + kPadC)) = col;
+      }
+      continue;
+    }
+    // padded coordinates this pixel writes: its own texel plus the ring texels that replicate it
+    const int oya = y == 0 ? 0 : y + kPadC, oyb = y == H - 1 ? OH - 1 : y + kPadC;
+    for (int oy = oya; oy <= oyb; ++oy) {
+      for (int ox = oxa; ox <= oxb; ++ox) {
+        const unsigned o = (unsigned)(oy * OW + ox);
+        at32(pc, o) = col;
+        at32(pb, o) = bia;
+        if (pt) {
+          at32(pt, (unsigned)tiled_index(tilesX, ox, oy)) = col;
         }
       }
     }
@@ -3138,20 +3363,47 @@ __global__ void k_temporal(TemporalFrames F, int W, int H, float sigma, int radi
   }
 }
 
+// One unmasked tap of the tiled temporal filter. FAST: expf_glibc_nonpos, for the parameters the host's
+// temporal_fast_tap_ok admits — all three weights in [0, inf) and 0 < sigma^2 < inf as computed here. The guide differences are integers of magnitude <= 65535,
+// so each e is finite with |e| <= 1; every weight * (e * e) is then finite and >= +0, their sum lies in [+0, +inf] and
+// is not NaN. Its negation lies in [-inf, -0]; the quotient multiplies it by the positive finite double 1 / sig2 and
+// rounds, which keeps it in [-inf, -0]: expf_glibc_nonpos's precondition, under which it returns expf_glibc's bits.
+template <bool FAST>
+__device__ __forceinline__ void temporal_tap(ushort4 ref, ushort4 sc, float centre, float weight0, float weight1,
+                                             float weight2, double rcpSig2, const unsigned long long* expTab,
+                                             float& weightedSumPix, float& sumWeight) {
+  const double rcp65535 = 1.0 / 65535.0;
+  const float e0 = div_int_by_const((int)ref.x - (int)sc.x, rcp65535);  // (float)diff / 65535.0f
+  const float e1 = div_int_by_const((int)ref.y - (int)sc.y, rcp65535);  // (float)diff / 65535.0f
+  const float e2 = div_int_by_const((int)ref.z - (int)sc.z, rcp65535);  // (float)diff / 65535.0f
+  const float weightedDiff = weight0 * (e0 * e0) + weight1 * (e1 * e1) + weight2 * (e2 * e2);
+  const float arg = div_by_const(-weightedDiff, rcpSig2);  // -weightedDiff / sig2
+  const float weight = FAST ? expf_glibc_nonpos(arg, expTab) : expf_glibc(arg, expTab);
+  weightedSumPix += centre * weight;
+  sumWeight += weight;
+}
+
 // The same filter with the window's taps staged through LDS: a 32 x 8 block loads, per window frame, the guide texels
 // and mask bytes of its tile + `radius` halo once (clamped coordinates, like the taps) and every pixel reads its
 // (2 radius + 1)^2 taps from there — the direct form issued 19 global loads per pixel per frame for radius 1 and sat at
 // a third of the VALU peak waiting for them. Same operations in the same order; two LDS buffers, one barrier per frame.
 // Dynamic LDS: 2 x (32 + 2 radius) x (8 + 2 radius) x 9 bytes (guide 8, mask 1), rounded up to 16.
+// RADIUS: the spatial radius as a compile-time constant (1, the level loop's at every level: taps unrolled, LDS offsets
+// constant), or -1 for the run-time `radius`. FAST: temporal_tap<true>, and each window frame's barrier is a block vote
+// over "every mask byte staged for this frame is set": when it holds, the frame's taps run without mask reads or
+// branches — the same taps in the same order. <-1, false> is the generic form (DERP_TEMPORAL_GENERIC=1, and whenever
+// the weights fall outside the predicate); the launcher picks (temporal_launch, derp_capi.hip).
+template <int RADIUS, bool FAST>
 __global__ void __launch_bounds__(256)
-    k_temporal_tiled(TemporalFrames F, int W, int H, float sigma, int radius, float weight0, float weight1, float weight2,
-                     float* __restrict__ out, const int* __restrict__ dst2src) {
+    k_temporal_tiled(TemporalFrames F, int W, int H, float sigma, int radiusArg, float weight0, float weight1,
+                     float weight2, float* __restrict__ out, const int* __restrict__ dst2src) {
   extern __shared__ unsigned char ldsTemporal[];
   __shared__ unsigned long long expTab[32];
   const int tid = threadIdx.y * blockDim.x + threadIdx.x;
   if (tid < 32) {
     expTab[tid] = kExp2fTab[tid];
   }
+  const int radius = RADIUS >= 0 ? RADIUS : radiusArg;
   const int TW = 32 + 2 * radius, TH = 8 + 2 * radius, cells = TW * TH;
   const size_t bufBytes = ((size_t)cells * 9 + 15) & ~(size_t)15;
   const int x0 = blockIdx.x * 32, y0 = blockIdx.y * 8;
@@ -3173,7 +3425,6 @@ __global__ void __launch_bounds__(256)
   }
   const float sig2 = sigma * sigma;
   const double rcpSig2 = 1.0 / (double)sig2;
-  const double rcp65535 = 1.0 / 65535.0;
   // Software pipeline over the window: the cells of frame t + 1 (the first two per thread: every cell up to radius 2)
   // and its centre value are loaded into registers before the taps of frame t run and stored to the other buffer after
   // them, so the global-load latency hides behind the taps. Guide texels are loaded whether or not their mask byte is
@@ -3190,6 +3441,7 @@ __global__ void __launch_bounds__(256)
   ushort4 nextG[2];
   unsigned char nextM[2];
   float centreNext = 0.f;
+  int stagedFull = 1;  // every mask byte this thread staged for the frame last stashed is set
   auto fetch = [&](int t) {
     const uint8_t* __restrict__ mask = F.masks[t] + pd;
     const ushort4* __restrict__ guide = F.guides[t] + pg;
@@ -3206,10 +3458,12 @@ __global__ void __launch_bounds__(256)
     unsigned char* buf = ldsTemporal + (size_t)(t & 1) * bufBytes;
     ushort4* tg = reinterpret_cast<ushort4*>(buf);
     unsigned char* tm = buf + (size_t)cells * 8;
+    stagedFull = 1;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int k = tid + i * 256;
       if (k < cells) {
+        stagedFull &= nextM[i] != 0;
         tm[k] = nextM[i];
         tg[k] = nextG[i];
       }
@@ -3221,7 +3475,9 @@ __global__ void __launch_bounds__(256)
         const int ty = k / TW, tx = k - ty * TW;
         const int sx = min(max(x0 - radius + tx, 0), W - 1), sy = min(max(y0 - radius + ty, 0), H - 1);
         const size_t j = (size_t)sy * W + sx;
-        tm[k] = mask[j];
+        const unsigned char mk = mask[j];
+        stagedFull &= mk != 0;
+        tm[k] = mk;
         tg[k] = guide[j];
       }
     }
@@ -3234,25 +3490,44 @@ __global__ void __launch_bounds__(256)
     const unsigned char* tm = buf + (size_t)cells * 8;
     const float centre = centreNext;
     // frame t's buffer is complete, and everyone has finished the taps of frame t - 1: its buffer takes frame t + 1
-    __syncthreads();
+    bool fullMask = false;  // (block-uniform) no cell of frame t's tile is masked
+    if (FAST) {
+      fullMask = __syncthreads_and(stagedFull) != 0;
+    } else {
+      __syncthreads();
+    }
     if (t + 1 < F.n) {
       fetch(t + 1);
     }
     if (active) {
-      for (int u = -radius; u <= radius; ++u) {
-        for (int v = -radius; v <= radius; ++v) {
-          const int k = ((int)threadIdx.y + radius + v) * TW + (int)threadIdx.x + radius + u;
-          if (!tm[k]) {
-            continue;
+      if (FAST && fullMask) {
+        if (RADIUS == 1) {
+          const ushort4* tc = tg + ((int)threadIdx.y + 1) * (32 + 2) + (int)threadIdx.x + 1;
+#pragma unroll
+          for (int u = -1; u <= 1; ++u) {
+#pragma unroll
+            for (int v = -1; v <= 1; ++v) {
+              temporal_tap<true>(ref, tc[v * (32 + 2) + u], centre, weight0, weight1, weight2, rcpSig2, expTab,
+                                 weightedSumPix, sumWeight);
+            }
           }
-          const ushort4 sc = tg[k];
-          const float e0 = div_int_by_const((int)ref.x - (int)sc.x, rcp65535);  // (float)diff / 65535.0f
-          const float e1 = div_int_by_const((int)ref.y - (int)sc.y, rcp65535);  // (float)diff / 65535.0f
-          const float e2 = div_int_by_const((int)ref.z - (int)sc.z, rcp65535);  // (float)diff / 65535.0f
-          const float weightedDiff = weight0 * (e0 * e0) + weight1 * (e1 * e1) + weight2 * (e2 * e2);
-          const float weight = expf_glibc(div_by_const(-weightedDiff, rcpSig2), expTab);  // -weightedDiff / sig2
-          weightedSumPix += centre * weight;
-          sumWeight += weight;
+        } else {
+          for (int u = -radius; u <= radius; ++u) {
+            for (int v = -radius; v <= radius; ++v) {
+              const int k = ((int)threadIdx.y + radius + v) * TW + (int)threadIdx.x + radius + u;
+              temporal_tap<true>(ref, tg[k], centre, weight0, weight1, weight2, rcpSig2, expTab, weightedSumPix, sumWeight);
+            }
+          }
+        }
+      } else {
+        for (int u = -radius; u <= radius; ++u) {
+          for (int v = -radius; v <= radius; ++v) {
+            const int k = ((int)threadIdx.y + radius + v) * TW + (int)threadIdx.x + radius + u;
+            if (!tm[k]) {
+              continue;
+            }
+            temporal_tap<FAST>(ref, tg[k], centre, weight0, weight1, weight2, rcpSig2, expTab, weightedSumPix, sumWeight);
+          }
         }
       }
     }

@@ -444,7 +444,10 @@ class Derp:
         h, w = self._shape(self._cur)
         spec = {"warp": (0, (h, w, 2), np.float32), "color": (2, (h, w, 3), np.uint16),
                 "bias": (3, (h, w, 3), np.uint16), "variance": (4, (h, w), np.float32),
-                "fov": (5, (h, w), np.uint8)}[which]
+                "fov": (5, (h, w), np.uint8),
+                # the colour tables as stored (2-texel replicated ring, u16 x 4 texels) and their blank-tile flags
+                "color_padded": (6, (h + 4, w + 4, 4), np.uint16), "bias_padded": (7, (h + 4, w + 4, 4), np.uint16),
+                "tile_seen": (8, ((h + 31) // 32, (w + 31) // 32), np.uint8)}[which]
         out = np.zeros(spec[1], dtype=spec[2])
         self._ck(lib().derp_debug_download(self.h, d, s, spec[0], _p(out)))
         return out

@@ -189,7 +189,9 @@ int derp_get_level_disparity(derp_ctx* ctx, int dst, float* disp);
 /* computeCost (Derp.cpp:104-226) of a caller-supplied disparity map at every interior pixel */
 int derp_cost_map(derp_ctx* ctx, int dst, const float* disp, float* cost, float* confidence);
 /* tables of the current level: which = 0 projWarp (float2), 2 projColor (u16x3), 3 projColorBias
- * (u16x3), 4 variance of src (float), 5 fov mask of dst (u8; src ignored) */
+ * (u16x3), 4 variance of src (float), 5 fov mask of dst (u8; src ignored), 6 / 7 projColor / projColorBias as stored:
+ * the padded (H + 4) x (W + 4) plane of u16x4 texels with its replicated 2-texel ring, 8 the table's blank-tile flags
+ * (u8 per 32 x 32 tile, row-major; 0 = no source pixel maps into the tile) */
 int derp_debug_download(derp_ctx* ctx, int dst, int src, int which, void* out);
 /* the cost kernels' own fp64 atan2 (FTHETA branch of Camera::cameraToSensor, Camera.h:306-309): out[i] =
  * atan2(y[i], x[i]) for y >= 0, as the device routine computes it — so that a test can hold it against libm */
