@@ -141,7 +141,7 @@ int block_trace_attach(derp_ctx* c, LevelView& V, int which, int gridX, int grid
   return 0;
 }
 
-// k_blur3_u16: 64 x 4 threads, each a column strip of kBlurRows rows
+// k_variance_bias: 64 x 4 threads, each a column strip of kBlurRows rows
 const dim3 kBlurBlk(64, 4, 1);
 dim3 blur_grid(int ow, int oh, int planes) {
   return dim3((ow + 63) / 64, (oh + 4 * kBlurRows - 1) / (4 * kBlurRows), planes);
@@ -190,6 +190,13 @@ int get_lanczos(derp_ctx* c, int ssize, int dsize, LanczosTab** out) {
     lanczos_coeffs(f, &coef[(size_t)d * 8]);
   }
   LanczosTab t;
+  // the most source positions a run of kLanczosH outputs reaches: first tap of its first output to last tap of its last
+  for (int d0 = 0; d0 < dsize; d0 += kLanczosH) {
+    const int d1 = std::min(d0 + kLanczosH, dsize) - 1;
+    const int lo = std::min(std::max(ofs[d0] - 3, 0), ssize - 1), hi = std::min(std::max(ofs[d1] + 4, 0), ssize - 1);
+    t.tileSpan = std::max(t.tileSpan, hi - lo + 1);
+    t.monotone = t.monotone && std::is_sorted(ofs.begin() + d0, ofs.begin() + d1 + 1);
+  }
   ALLOC(c, t.ofs, ofs.size() * sizeof(int));
   ALLOC(c, t.coef, coef.size() * sizeof(float));
   HIPCHK(c, hipMemcpyAsync(t.ofs.p, ofs.data(), ofs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -341,6 +348,14 @@ int upsample_lanczos_dev(derp_ctx* c, const float* in, int sw, int sh, float* ou
   LanczosTab *tx, *ty;
   TRY(get_lanczos(c, sw, dw, &tx));
   TRY(get_lanczos(c, sh, dh, &ty));
+  if (ty->monotone && ty->tileSpan <= kLanczosRows) {
+    hipLaunchKernelGGL(k_lanczos, dim3((dw + kLanczosW - 1) / kLanczosW, (dh + kLanczosH - 1) / kLanczosH, planes),
+                       dim3(kLanczosW, 4), 0, c->stream, in, sw, sh, dw, dh, tx->ofs.as<int>(), tx->coef.as<float>(),
+                       ty->ofs.as<int>(), ty->coef.as<float>(), out, inStride, outStride);
+    KCHECK(c);
+    return 0;
+  }
+  // a tile that reaches over more source rows than the kernel's window holds (downsampling): the two passes
   const size_t tmpStride = (size_t)dw * sh;
   ALLOC(c, c->w.lanczosTmp, tmpStride * planes * sizeof(float));
   hipLaunchKernelGGL(k_lanczos_h, grid2d(dw, sh, planes, kBlk2d), kBlk2d, 0, c->stream, in, sw, sh, dw,
@@ -554,7 +569,19 @@ int run_random_proposals(derp_ctx* c, int dst0, int nd) {
   c->randomRanThisLevel = true;
   LevelView V = make_view(c, ST_RANDOM, dst0, nd);
   if (V.H > 2 && V.W > 2) {
-    hipLaunchKernelGGL(k_row_rank, dim3(V.H - 2, nd), dim3(256), 0, c->stream, V, c->w.rank.as<int>());
+    // (a^P)^k for every count k of gated-in pixels a row can hold: built when P changes or a wider level arrives
+    WorkSet& w = c->w;
+    if (w.rankPowersP != V.randomProposals || w.rankPowersN < V.W) {
+      const int count = *std::max_element(c->LW.begin(), c->LW.end());  // the widest level: once per pyramid
+      ALLOC(c, w.rankPowers, (size_t)count * sizeof(uint32_t));
+      hipLaunchKernelGGL(k_minstd_powers, dim3(blocks_of(count, 256)), dim3(256), 0, c->stream, V.randomProposals, count,
+                         w.rankPowers.as<uint32_t>());
+      KCHECK(c);
+      w.rankPowersP = V.randomProposals;
+      w.rankPowersN = count;
+    }
+    hipLaunchKernelGGL(k_row_rank, dim3(V.H - 2, nd), dim3(256), 0, c->stream, V, w.rankPowers.as<uint32_t>(),
+                       w.rank.as<int>());
     KCHECK(c);
   }
   int tilesX;
@@ -759,15 +786,11 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   }
   TRY(compute_fov_and_masks(c, level));
   {
+    // the variance and the own colour bias come from one pass over the colour plane: the pass reports under `variance`,
+    // and `own_bias` reads 0
     Span sp(c, ST_VARIANCE, level);
-    hipLaunchKernelGGL(k_variance, grid2d(W, H, c->S, kBlk2d), kBlk2d, 0, c->stream, c->frame().color[level].as<ushort4>(),
-                       W, H, c->w.srcVar.as<float>());
-    KCHECK(c);
-  }
-  {
-    Span sp(c, ST_OWN_BIAS, level);
-    hipLaunchKernelGGL(k_blur3_u16, blur_grid(W, H, c->S), kBlurBlk, 0, c->stream,
-                       c->frame().color[level].as<ushort4>(), 0, c->w.ownBias.as<ushort4>(), 0, W, H, n, n);
+    hipLaunchKernelGGL(k_variance_bias, blur_grid(W, H, c->S), kBlurBlk, 0, c->stream, c->frame().color[level].as<ushort4>(),
+                       W, H, c->w.srcVar.as<float>(), c->w.ownBias.as<ushort4>());
     KCHECK(c);
   }
   // fresh PyramidLevel: disparity / cost / confidence start at 0 (PyramidLevel.h:209-221)

@@ -43,6 +43,10 @@ struct TimedSpan {
 
 struct LanczosTab {
   DevBuf ofs, coef;
+  // as the vertical table of k_lanczos: the source rows one output tile needs at the most, and whether the offsets never
+  // decrease (they do not; the kernel's row window rests on it)
+  int tileSpan = 0;
+  bool monotone = true;
 };
 
 struct AreaTabDev {  // computeResizeAreaTab of one axis, resident in HBM
@@ -54,6 +58,8 @@ struct AreaTabDev {  // computeResizeAreaTab of one axis, resident in HBM
 // level (projWarp, projWarpInv, rayDir, behind, resampling tables) are shared by the lanes and stay on the context.
 struct WorkSet {
   DevBuf srcVar, ownBias, maskAnd, disparity, cost, confidence, dispRes, costRes, changed, tmpF, rank, mismatchMask, pairCount;
+  DevBuf rankPowers;  // k_row_rank: (a^P)^k mod m for k < rankPowersN, P = rankPowersP (k_minstd_powers)
+  int rankPowersP = -1, rankPowersN = 0;
   DevBuf tileSeen;    // k_reproject_bias: per (table, tile) whether any map position is valid
   DevBuf projColor, projBias;
   DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)

@@ -104,6 +104,27 @@ int derp_debug_download(derp_ctx* c, int d, int s, int which, void* out) {
     HIPCHK(c, hipMemcpy(out, c->fovMask.as<uint8_t>() + (size_t)d * n, n, hipMemcpyDeviceToHost));
     return 0;
   }
+  if (which == 9) {  // the own colour bias of source `s`, as u16 x 3
+    if (s < 0 || s >= c->S) {
+      return fail(c, "bad source index");
+    }
+    std::vector<ushort4> tmp(n);
+    HIPCHK(c, hipMemcpy(tmp.data(), c->w.ownBias.as<ushort4>() + (size_t)s * n, n * sizeof(ushort4), hipMemcpyDeviceToHost));
+    uint16_t* o = reinterpret_cast<uint16_t*>(out);
+    for (size_t i = 0; i < n; ++i) {
+      o[i * 3 + 0] = tmp[i].x;
+      o[i * 3 + 1] = tmp[i].y;
+      o[i * 3 + 2] = tmp[i].z;
+    }
+    return 0;
+  }
+  if (which == 10) {  // k_row_rank's engine states of destination `d`: defined at the gated-in interior pixels only
+    if (d < 0 || d >= c->D) {
+      return fail(c, "bad destination index");
+    }
+    HIPCHK(c, hipMemcpy(out, c->w.rank.as<int>() + (size_t)d * n, n * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+  }
   if (d < 0 || d >= c->D || s < 0 || s >= c->S || s == c->dst2srcH[d]) {
     return fail(c, "bad (dst, src) pair");
   }

@@ -1110,112 +1110,79 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 }
 
 // computeImageVariance — DerpUtil.cpp:214-237 (cv::blur 3x3 on CV_32FC3: double row sums,
-// double column sums, * 1/9 -> float; BORDER_REFLECT_101), PyramidLevel.h:232-247
-__global__ void k_variance(const ushort4* __restrict__ color, int W, int H, float* __restrict__ var) {
-  const int s = blockIdx.z;
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (x >= W || y >= H) {
-    return;
-  }
-  const ushort4* img = color + (size_t)s * W * H;
-  const float scale = 1.0f / 65535.0f;
-  double sum[3] = {0, 0, 0}, sumSq[3] = {0, 0, 0};
-  const int xs[3] = {reflect101(x - 1, W), x, reflect101(x + 1, W)};
-  for (int j = -1; j <= 1; ++j) {
-    const int yy = reflect101(y + j, H);
-    double rs[3], rq[3];
-    {
-      const ushort4 q0 = img[(size_t)yy * W + xs[0]], q1 = img[(size_t)yy * W + xs[1]], q2 = img[(size_t)yy * W + xs[2]];
-      const float f0[3] = {q0.x * scale, q0.y * scale, q0.z * scale};
-      const float f1[3] = {q1.x * scale, q1.y * scale, q1.z * scale};
-      const float f2[3] = {q2.x * scale, q2.y * scale, q2.z * scale};
-      for (int c = 0; c < 3; ++c) {
-        rs[c] = (double)f0[c] + (double)f1[c] + (double)f2[c];
-        rq[c] = (double)(f0[c] * f0[c]) + (double)(f1[c] * f1[c]) + (double)(f2[c] * f2[c]);
-      }
-    }
-    for (int c = 0; c < 3; ++c) {
-      sum[c] += rs[c];
-      sumSq[c] += rq[c];
-    }
-  }
-  const double k = 1. / 9;
-  float v[3];
-  for (int c = 0; c < 3; ++c) {
-    const float mean = (float)(sum[c] * k);
-    const float meanSq = (float)(sumSq[c] * k);
-    v[c] = meanSq - mean * mean;
-  }
-  // varChannels[0]*w[2] + varChannels[1]*w[1] + varChannels[2]*w[0], kRgbWeights = {.3333,.3334,.3333}
-  const float t = v[0] * 0.3333f + v[1] * 0.3334f;
-  var[(size_t)s * W * H + (size_t)y * W + x] = t * 1.0f + v[2] * 0.3333f;
-}
-
-// colorBias = cv::blur 3x3 on CV_16UC3 (DerpUtil.cpp:208-210): exact integer sum, round(sum/9).
-// Source and destination may carry replicated rings (padIn / padOut); the blur itself uses
-// BORDER_REFLECT_101 over the image interior, and ring texels repeat the clamped interior value.
-// One thread = one column of kBlurRows consecutive output rows. Away from the borders the three
-// horizontal 3-sums of a column slide down the rows (3 loads per output instead of 9); threads whose
-// strip touches a border, where BORDER_REFLECT_101 / the ring replication change the tap pattern, take
-// the texel-by-texel form for their rows.
+// double column sums, * 1/9 -> float; BORDER_REFLECT_101), PyramidLevel.h:232-247 — and the camera's own
+// colorBias = cv::blur 3x3 on CV_16UC3 (DerpUtil.cpp:208-210): exact integer sum, round(sum/9), same border.
+// Both are 3x3 boxes over the same colour plane, so one pass serves them. One thread = one column of
+// kBlurRows consecutive output rows: the three-texel horizontal sums of a row (integer for the bias, fp64
+// sums of the scaled values and of their squares for the variance) are formed once and slide down the
+// strip. The row sum of row yy at column x is the same expression for the three output rows that use it, and
+// the column sums add the rows in the order j = -1, 0, 1, so every value keeps the bits of the one-pixel form.
 constexpr int kBlurRows = 8;
-__device__ __forceinline__ ushort4 blur3_texel(const ushort4* __restrict__ img, int IW, int padIn, int W, int H, int x,
-                                               int y) {
-  unsigned s0 = 0, s1 = 0, s2 = 0;
-  for (int j = -1; j <= 1; ++j) {
-    const int yy = reflect101(y + j, H) + padIn;
-    for (int i = -1; i <= 1; ++i) {
-      const int xx = reflect101(x + i, W) + padIn;
-      const ushort4 q = img[(size_t)yy * IW + xx];
-      s0 += q.x;
-      s1 += q.y;
-      s2 += q.z;
-    }
-  }
-  return make_ushort4((unsigned short)((s0 + 4) / 9), (unsigned short)((s1 + 4) / 9), (unsigned short)((s2 + 4) / 9), 0);
-}
-__global__ void k_blur3_u16(const ushort4* __restrict__ in, int padIn, ushort4* __restrict__ out, int padOut, int W,
-                            int H, size_t planeIn, size_t planeOut) {
-  const int p = blockIdx.z;
-  const int ox = blockIdx.x * blockDim.x + threadIdx.x;
-  const int oy0 = (blockIdx.y * blockDim.y + threadIdx.y) * kBlurRows;
-  const int OW = W + 2 * padOut, OH = H + 2 * padOut;
-  if (ox >= OW || oy0 >= OH) {
+struct BoxRow {
+  unsigned h[3];
+  double rs[3], rq[3];
+};
+__global__ void __launch_bounds__(256) k_variance_bias(const ushort4* __restrict__ color, int W, int H,
+                                                       float* __restrict__ var, ushort4* __restrict__ bias) {
+  const int s = blockIdx.z;
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * kBlurRows;
+  if (x >= W || y0 >= H) {
     return;
   }
-  const ushort4* img = in + (size_t)p * planeIn;
-  ushort4* dst = out + (size_t)p * planeOut;
-  const int IW = W + 2 * padIn;
-  const int x = ox - padOut, y0 = oy0 - padOut;
-  if (x >= 1 && x <= W - 2 && y0 >= 1 && y0 + kBlurRows - 1 <= H - 2) {
-    auto hsum = [&](int y, unsigned (&h)[3]) {
-      const ushort4* r = img + (size_t)(y + padIn) * IW + (x + padIn);
-      const ushort4 a = r[-1], b = r[0], c = r[1];
-      h[0] = (unsigned)a.x + b.x + c.x;
-      h[1] = (unsigned)a.y + b.y + c.y;
-      h[2] = (unsigned)a.z + b.z + c.z;
-    };
-    unsigned hp[3], hc[3], hn[3];
-    hsum(y0 - 1, hp);
-    hsum(y0, hc);
+  const size_t n = (size_t)W * H;
+  const ushort4* img = color + (size_t)s * n;
+  const int xl = reflect101(x - 1, W), xr = reflect101(x + 1, W);
+  const float scale = 1.0f / 65535.0f;
+  auto row_sums = [&](int y, BoxRow& r) {
+    const ushort4* line = img + (size_t)reflect101(y, H) * W;
+    const ushort4 q0 = line[xl], q1 = line[x], q2 = line[xr];
+    r.h[0] = (unsigned)q0.x + q1.x + q2.x;
+    r.h[1] = (unsigned)q0.y + q1.y + q2.y;
+    r.h[2] = (unsigned)q0.z + q1.z + q2.z;
+    const float f0[3] = {q0.x * scale, q0.y * scale, q0.z * scale};
+    const float f1[3] = {q1.x * scale, q1.y * scale, q1.z * scale};
+    const float f2[3] = {q2.x * scale, q2.y * scale, q2.z * scale};
 #pragma unroll
-    for (int r = 0; r < kBlurRows; ++r) {
-      hsum(y0 + r + 1, hn);
-      dst[(size_t)(oy0 + r) * OW + ox] =
-          make_ushort4((unsigned short)((hp[0] + hc[0] + hn[0] + 4) / 9), (unsigned short)((hp[1] + hc[1] + hn[1] + 4) / 9),
-                       (unsigned short)((hp[2] + hc[2] + hn[2] + 4) / 9), 0);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        hp[c] = hc[c];
-        hc[c] = hn[c];
-      }
+    for (int c = 0; c < 3; ++c) {
+      r.rs[c] = (double)f0[c] + (double)f1[c] + (double)f2[c];
+      r.rq[c] = (double)(f0[c] * f0[c]) + (double)(f1[c] * f1[c]) + (double)(f2[c] * f2[c]);
     }
-    return;
-  }
-  const int xc = min(max(x, 0), W - 1);
-  for (int r = 0; r < kBlurRows && oy0 + r < OH; ++r) {
-    const int yc = min(max(y0 + r, 0), H - 1);
-    dst[(size_t)(oy0 + r) * OW + ox] = blur3_texel(img, IW, padIn, W, H, xc, yc);
+  };
+  BoxRow rp, rc, rn;
+  row_sums(y0 - 1, rp);
+  row_sums(y0, rc);
+  const double k = 1. / 9;
+#pragma unroll
+  for (int r = 0; r < kBlurRows; ++r) {
+    const int y = y0 + r;
+    if (y >= H) {
+      break;
+    }
+    row_sums(y + 1, rn);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      double sum = 0, sumSq = 0;
+      sum += rp.rs[c];
+      sumSq += rp.rq[c];
+      sum += rc.rs[c];
+      sumSq += rc.rq[c];
+      sum += rn.rs[c];
+      sumSq += rn.rq[c];
+      const float mean = (float)(sum * k);
+      const float meanSq = (float)(sumSq * k);
+      v[c] = meanSq - mean * mean;
+    }
+    // varChannels[0]*w[2] + varChannels[1]*w[1] + varChannels[2]*w[0], kRgbWeights = {.3333,.3334,.3333}
+    const float t = v[0] * 0.3333f + v[1] * 0.3334f;
+    const size_t idx = (size_t)y * W + x;
+    var[(size_t)s * n + idx] = t * 1.0f + v[2] * 0.3333f;
+    bias[(size_t)s * n + idx] = make_ushort4((unsigned short)((rp.h[0] + rc.h[0] + rn.h[0] + 4) / 9),
+                                             (unsigned short)((rp.h[1] + rc.h[1] + rn.h[1] + 4) / 9),
+                                             (unsigned short)((rp.h[2] + rc.h[2] + rn.h[2] + 4) / 9), 0);
+    rp = rc;
+    rc = rn;
   }
 }
 
@@ -1861,7 +1828,7 @@ __global__ void k_brute_margin(LevelView V) {
 // ----------------------------------------------------------------------------------------
 // random proposals — Derp.cpp:750-873. The reference walks each row with one engine seeded
 // y * level; a pixel's draws start at numProposals * (#gated-in pixels to its left).
-// k_row_rank computes that count and leaves the engine's state at that position for every pixel.
+// k_row_rank computes that count and leaves the engine's state at that position for every gated-in pixel.
 // ----------------------------------------------------------------------------------------
 __device__ __forceinline__ bool random_gate(const LevelView& V, int d, int own, size_t idx) {
   const size_t n = (size_t)V.W * V.H;
@@ -1873,37 +1840,47 @@ __device__ __forceinline__ bool random_gate(const LevelView& V, int d, int own, 
   return !(V.srcVar[(size_t)own * n + idx] < thresh);
 }
 
-__global__ void __launch_bounds__(256) k_row_rank(LevelView V, int* __restrict__ rank) {
-  __shared__ int partial[256];
+// powers[k] = (a^P)^k mod m for k < count: the engine's multiplier over the draws of k gated-in pixels. It depends on P
+// alone, so one table serves every row, destination and level.
+__global__ void k_minstd_powers(int proposals, int count, uint32_t* __restrict__ powers) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < count) {
+    powers[k] = minstd_jump(1u, (uint64_t)proposals * (uint64_t)k);
+  }
+}
+
+// One block per (row, destination), 256 pixels of the row's interior per step: lane = pixel, so the gate's planes are
+// read in whole lines and the gate is evaluated once. The count of gated-in pixels to the left comes from the waves'
+// ballots (the bits below the lane, the waves before it through LDS, the steps before it in a running total), and the
+// engine's state in front of a gated-in pixel is seed_state(y * level) * (a^P)^k mod m with the power from `powers`
+// (the integer identity minstd_jump rests on). k_random_proposals reads the state of gated-in pixels only, and only
+// those are stored.
+__global__ void __launch_bounds__(256) k_row_rank(LevelView V, const uint32_t* __restrict__ powers, int* __restrict__ rank) {
+  __shared__ int waveCount[2][4];
   const int d = V.dst0 + blockIdx.y, y = blockIdx.x + 1;
   const int own = V.dst2src[d];
   const size_t n = (size_t)V.W * V.H;
-  const int inner = V.W - 2;
-  const int per = (inner + 255) / 256;
-  const int x0 = 1 + threadIdx.x * per, x1 = min(x0 + per, V.W - 1);
-  int cnt = 0;
-  for (int x = x0; x < x1; ++x) {
-    cnt += random_gate(V, d, own, (size_t)y * V.W + x);
-  }
-  partial[threadIdx.x] = cnt;
-  __syncthreads();
-  // exclusive scan of 256 partials (Hillis-Steele)
-  for (int off = 1; off < 256; off <<= 1) {
-    const int v = ((int)threadIdx.x >= off) ? partial[threadIdx.x - off] : 0;
-    __syncthreads();
-    partial[threadIdx.x] += v;
-    __syncthreads();
-  }
-  // the engine's state in front of every pixel's draws: one O(log n) jump to the thread's first pixel, then one
-  // multiplication by a^P per gated-in pixel (the random-proposal kernel used to jump per pixel: ~60 dependent
-  // 64-bit multiply-reduce steps at the head of every pixel's chain)
-  const int run = partial[threadIdx.x] - cnt;
-  uint32_t state = minstd_jump(minstd_seed(y * V.level), (uint64_t)V.randomProposals * (uint64_t)run);
-  const uint32_t aP = minstd_jump(1u, (uint64_t)V.randomProposals);
-  for (int x = x0; x < x1; ++x) {
-    rank[(size_t)d * n + (size_t)y * V.W + x] = (int)state;
-    if (random_gate(V, d, own, (size_t)y * V.W + x)) {
-      state = minstd_mulmod(state, aP);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t seed = minstd_seed(y * V.level);
+  int before = 0;  // gated-in pixels of the steps so far
+  for (int xb = 1, step = 0; xb < V.W - 1; xb += 256, ++step) {
+    const int x = xb + (int)threadIdx.x;
+    const size_t idx = (size_t)y * V.W + x;
+    const bool go = x < V.W - 1 && random_gate(V, d, own, idx);
+    const unsigned long long ballot = __ballot(go);
+    if (lane == 0) {
+      waveCount[step & 1][wave] = __popcll(ballot);
+    }
+    __syncthreads();  // (one per step: the two halves of waveCount alternate)
+    int k = before + __popcll(ballot & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int t = waveCount[step & 1][w];
+      k += w < wave ? t : 0;
+      before += t;
+    }
+    if (go) {
+      rank[(size_t)d * n + idx] = (int)minstd_mulmod(seed, powers[k]);
     }
   }
 }
@@ -2796,6 +2773,9 @@ __global__ void __launch_bounds__(256)
 // the two middle values (in double, as the reference's "/ 2.0"). Radius 1 (the value DerpCLI uses,
 // Derp.h:36) keeps the 9 candidates in registers and orders them with a 25-exchange sorting network,
 // invalid taps as +inf; the result depends only on the multiset of values, not on the sort used.
+// The radius-1 path stages the block's taps in LDS and so needs a block of at most kMedianBlkW x kMedianBlkH
+// threads (kBlk2d, which every launch uses).
+constexpr int kMedianBlkW = 32, kMedianBlkH = 8;
 __device__ __forceinline__ void cswap(float& a, float& b) {
   const float lo = fminf(a, b), hi = fmaxf(a, b);
   a = lo;
@@ -2805,14 +2785,35 @@ __device__ __forceinline__ void cswap(float& a, float& b) {
 __global__ void k_masked_median(const float* __restrict__ image, const float* __restrict__ background,
                                 const uint8_t* __restrict__ mask, int W, int H, int radius, float* __restrict__ out,
                                 size_t planeStride, const uint8_t* __restrict__ fovForNan) {
+  __shared__ float taps[kMedianBlkH + 2][kMedianBlkW + 2];
   const int p = blockIdx.z;
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+  const float* img = image + (size_t)p * planeStride;
+  const uint8_t* m = mask + (size_t)p * planeStride;
+  if (radius == 1) {
+    // the block's pixels and a one-pixel ring, once: a valid tap as its value, every other one (out of bounds, outside
+    // the mask, 0, NaN) as NaN — 1.3 value and mask loads per pixel where the tap-by-tap form made 18
+    const int tw = (int)blockDim.x + 2, th = (int)blockDim.y + 2;
+    const int x0 = (int)(blockIdx.x * blockDim.x) - 1, y0 = (int)(blockIdx.y * blockDim.y) - 1;
+    for (int i = threadIdx.y * blockDim.x + threadIdx.x; i < tw * th; i += blockDim.x * blockDim.y) {
+      const int ty = i / tw, tx = i - ty * tw;
+      const int yy = y0 + ty, xx = x0 + tx;
+      float t = __builtin_nanf("");
+      if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+        const size_t q = (size_t)yy * W + xx;
+        const float val = img[q];
+        if (m[q] && val != 0) {
+          t = val;
+        }
+      }
+      taps[ty][tx] = t;
+    }
+    __syncthreads();
+  }
   if (x >= W || y >= H) {
     return;
   }
   const size_t idx = (size_t)y * W + x;
-  const float* img = image + (size_t)p * planeStride;
-  const uint8_t* m = mask + (size_t)p * planeStride;
   float result = 0.0f;
   if (!m[idx]) {
     if (background) {
@@ -2826,17 +2827,10 @@ __global__ void k_masked_median(const float* __restrict__ image, const float* __
     for (int j = 0; j < 3; ++j) {
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const int yy = y + j - 1, xx = x + i - 1;
-        float t = inf;
-        if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-          const size_t q = (size_t)yy * W + xx;
-          const float val = img[q];
-          if (m[q] && !isnan(val) && val != 0) {
-            t = val;
-            ++cnt;
-          }
-        }
-        v[j * 3 + i] = t;
+        const float val = taps[threadIdx.y + j][threadIdx.x + i];
+        const bool valid = !isnan(val);
+        cnt += valid;
+        v[j * 3 + i] = valid ? val : inf;
       }
     }
     // 9-input sorting network (25 compare-exchanges)
@@ -2969,6 +2963,57 @@ __global__ void k_lanczos_v(const float* __restrict__ tmp, int SH, int DW, int D
   }
   out[(size_t)p * outStride + (size_t)dy * DW + x] =
       r[0] * b[0] + r[1] * b[1] + r[2] * b[2] + r[3] * b[3] + r[4] * b[4] + r[5] * b[5] + r[6] * b[6] + r[7] * b[7];
+}
+// Both passes in one kernel, without the full-size intermediate: a block of kLanczosW x 4 threads forms the horizontal
+// results of the source rows its kLanczosW x kLanczosH output tile needs in LDS (k_lanczos_h's expression per value),
+// then takes the vertical sums from there (k_lanczos_v's expression). yofs does not decrease with dy, so the tile's
+// rows lie between the first tap of its first output row and the last tap of its last; the launcher takes this kernel
+// where no tile needs more than kLanczosRows source rows (every ratio >= 1, that is every upsampling), the pair above
+// otherwise.
+constexpr int kLanczosW = 64, kLanczosH = 32, kLanczosRows = 40;
+__global__ void __launch_bounds__(256) k_lanczos(const float* __restrict__ in, int SW, int SH, int DW, int DH,
+                                                 const int* __restrict__ xofs, const float* __restrict__ alpha,
+                                                 const int* __restrict__ yofs, const float* __restrict__ beta,
+                                                 float* __restrict__ out, size_t inStride, size_t outStride) {
+  __shared__ float rows[kLanczosRows][kLanczosW];
+  const int p = blockIdx.z;
+  const int dx = blockIdx.x * kLanczosW + threadIdx.x;
+  const int dy0 = blockIdx.y * kLanczosH, dy1 = min(dy0 + kLanczosH, DH) - 1;
+  const int rowLo = min(max(yofs[dy0] - 3, 0), SH - 1), rowHi = min(max(yofs[dy1] + 4, 0), SH - 1);
+  if (dx < DW) {
+    const float* a = alpha + (size_t)dx * 8;
+    const int sx = xofs[dx] - 3;
+    for (int r = threadIdx.y; r <= rowHi - rowLo && r < kLanczosRows; r += blockDim.y) {
+      const float* S = in + (size_t)p * inStride + (size_t)(rowLo + r) * SW;
+      float v = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int sxj = min(max(sx + j, 0), SW - 1);
+        float sv = S[sxj];
+        if (sv != sv) {
+          sv = 1e-4f;  // OpenCV doesn't handle NaNs: NaN -> minDisp (UpsampleDisparityLib.cpp:141-144)
+        }
+        v += sv * a[j];
+      }
+      rows[r][threadIdx.x] = v;
+    }
+  }
+  __syncthreads();
+  if (dx >= DW) {
+    return;
+  }
+  for (int dy = dy0 + threadIdx.y; dy <= dy1; dy += blockDim.y) {
+    const float* b = beta + (size_t)dy * 8;
+    const int sy = yofs[dy] - 3;
+    float r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int syk = min(max(sy + k, 0), SH - 1);
+      r[k] = rows[min(syk - rowLo, kLanczosRows - 1)][threadIdx.x];
+    }
+    out[(size_t)p * outStride + (size_t)dy * DW + dx] =
+        r[0] * b[0] + r[1] * b[1] + r[2] * b[2] + r[3] * b[3] + r[4] * b[4] + r[5] * b[5] + r[6] * b[6] + r[7] * b[7];
+  }
 }
 
 // masked path, steps 1-3: coarse value outside (fov & fg) -> NaN, INTER_NEAREST, NaN outside maskUp

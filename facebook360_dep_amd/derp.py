@@ -447,7 +447,10 @@ class Derp:
                 "fov": (5, (h, w), np.uint8),
                 # the colour tables as stored (2-texel replicated ring, u16 x 4 texels) and their blank-tile flags
                 "color_padded": (6, (h + 4, w + 4, 4), np.uint16), "bias_padded": (7, (h + 4, w + 4, 4), np.uint16),
-                "tile_seen": (8, ((h + 31) // 32, (w + 31) // 32), np.uint8)}[which]
+                "tile_seen": (8, ((h + 31) // 32, (w + 31) // 32), np.uint8),
+                # source s's own colour bias; destination d's engine states in front of its gated-in pixels (minstd_rand0,
+                # written by the random-proposal stage; the other pixels hold nothing meaningful)
+                "own_bias": (9, (h, w, 3), np.uint16), "rank": (10, (h, w), np.uint32)}[which]
         out = np.zeros(spec[1], dtype=spec[2])
         self._ck(lib().derp_debug_download(self.h, d, s, spec[0], _p(out)))
         return out

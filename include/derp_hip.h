@@ -191,7 +191,9 @@ int derp_cost_map(derp_ctx* ctx, int dst, const float* disp, float* cost, float*
 /* tables of the current level: which = 0 projWarp (float2), 2 projColor (u16x3), 3 projColorBias
  * (u16x3), 4 variance of src (float), 5 fov mask of dst (u8; src ignored), 6 / 7 projColor / projColorBias as stored:
  * the padded (H + 4) x (W + 4) plane of u16x4 texels with its replicated 2-texel ring, 8 the table's blank-tile flags
- * (u8 per 32 x 32 tile, row-major; 0 = no source pixel maps into the tile) */
+ * (u8 per 32 x 32 tile, row-major; 0 = no source pixel maps into the tile), 9 the own colour bias of src (u16x3; dst
+ * ignored), 10 the random proposals' engine states of dst (u32; src ignored; defined at the gated-in interior pixels only,
+ * after derp_stage_random_proposals) */
 int derp_debug_download(derp_ctx* ctx, int dst, int src, int which, void* out);
 /* the cost kernels' own fp64 atan2 (FTHETA branch of Camera::cameraToSensor, Camera.h:306-309): out[i] =
  * atan2(y[i], x[i]) for y >= 0, as the device routine computes it — so that a test can hold it against libm */

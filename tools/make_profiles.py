@@ -180,11 +180,11 @@ entry = {
     "ping_pong_level0_wave_cycle_shares": pp.get("wave_cycle_shares"),
     "ping_pong_level0_hbm_bytes_per_launch": pp.get("hbm_bytes_per_launch"),
     "kernels_level0_launch": {n: kernel_view(n) for n in
-                              ("k_ping_pong(", "k_random_proposals", "k_reproject_bias", "k_proj_warp_inv", "k_blur3_u16",
+                              ("k_ping_pong(", "k_random_proposals", "k_reproject_bias", "k_proj_warp_inv", "k_variance_bias",
                                "k_joint_bilateral", "k_temporal", "k_proj_warp(", "k_brute_costs")},
     "all_launches_fetch_bytes": {n: 2.0 * 1024.0 * val("FETCH_SIZE", n, "FETCH_SIZE", "sum") for n in
                                  ("k_ping_pong(", "k_random_proposals", "k_reproject_bias", "k_proj_warp_inv", "k_proj_warp(",
-                                  "k_joint_bilateral", "k_blur3_u16", "k_masked_median", "k_brute_costs", "k_temporal")},
+                                  "k_joint_bilateral", "k_variance_bias", "k_masked_median", "k_brute_costs", "k_temporal")},
 }
 for n, view in entry["kernels_level0_launch"].items():
     im = issue_model(n, view)
