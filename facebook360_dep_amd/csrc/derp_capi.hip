@@ -27,6 +27,7 @@
 #include "derp_render.h"
 #include "derp_geometric.h"
 #include "derp_sweep.h"
+#include "derp_align.h"
 
 using namespace derp;
 
@@ -1625,6 +1626,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
 #include "derp_mesh_api.h"
 #include "derp_geometric_api.h"
 #include "derp_sweep_api.h"
+#include "derp_align_api.h"
 #include "derp_filters_api.h"
 #include "derp_debug_api.h"
 #include "derp_sequence.h"

@@ -134,6 +134,7 @@ EXPORTS = [
     "derp_gc_run", "derp_gc_result", "derp_gc_stage", "derp_gc_slice_count",
     "derp_sweep_upload", "derp_sweep_overlaps", "derp_sweep_equirect_bounds", "derp_sweep_equirect",
     "derp_sweep_overlap_disparities", "derp_sweep_equirect_depths", "derp_sweep_crop_size", "derp_rig_center",
+    "derp_align_derive_cameras", "derp_align_setup", "derp_align_maps", "derp_align_frame",
 ]
 
 _lib = None
@@ -908,6 +909,37 @@ class Derp:
                                            int(bool(u8)), _p(out)))
         return out
 
+    # ---- AlignColors: red and blue resampled onto the green rig
+    def align_setup(self, red_ref, green_ref, blue_ref):
+        """red_ref / green_ref / blue_ref: the cameras (dicts) of the three reference rigs, one each; builds the warp
+        maps of every camera of this context's rig"""
+        rigs = [(CameraDesc * max(len(r), 1))(*[camera_desc(cam) for cam in r]) for r in (red_ref, green_ref, blue_ref)]
+        self._ck(lib().derp_align_setup(self.h, rigs[0], len(red_ref), rigs[1], len(green_ref), rigs[2], len(blue_ref)))
+
+    def _align_shape(self, cam):
+        if not 0 <= cam < self.D:
+            raise DerpError("bad camera index %d (the context has %d)" % (cam, self.D))
+        return int(self.cams_dst[cam]["resolution"][1]), int(self.cams_dst[cam]["resolution"][0])
+
+    def align_maps(self, cam):
+        """-> (red, blue), each [h, w, 2] float32: where pixel (x, y) of the green grid samples its channel"""
+        h, w = self._align_shape(cam)
+        red, blue = np.zeros((h, w, 2), np.float32), np.zeros((h, w, 2), np.float32)
+        self._ck(lib().derp_align_maps(self.h, int(cam), _p(red), _p(blue)))
+        return red, blue
+
+    def align_frame(self, images):
+        """images: per camera BGR uint16 [h, w, 3] -> the aligned images, same shapes"""
+        assert len(images) == self.D
+        ims = [np.ascontiguousarray(im, dtype=np.uint16) for im in images]
+        assert all(im.ndim == 3 and im.shape[2] == 3 for im in ims)
+        outs = [np.zeros_like(im) for im in ims]
+        ints = lambda v: (C.c_int * self.D)(*[int(x) for x in v])  # noqa: E731
+        src = (C.c_void_p * self.D)(*[im.ctypes.data for im in ims])
+        dst = (C.c_void_p * self.D)(*[o.ctypes.data for o in outs])
+        self._ck(lib().derp_align_frame(self.h, src, ints([im.shape[1] for im in ims]), ints([im.shape[0] for im in ims]), dst))
+        return outs
+
     def device_name(self):
         buf = C.create_string_buffer(256)
         self._ck(lib().derp_device_name(self.h, buf, 256))
@@ -967,6 +999,23 @@ def rig_center(cams, index):
             cam[k] = [float(v) for v in getattr(j, k)]
         out.append(cam)
     return out
+
+
+def align_derive_cameras(green, red_ref, green_ref, blue_ref):
+    """AlignColors' red and blue models of the calibrated camera `green` (dicts in, dicts out), on the host: the green
+    camera with the reference channel's focal times a float ratio, {s, -s}, and the reference channel's distortion"""
+    a = [camera_desc(c) for c in (green, red_ref, green_ref, blue_ref)]
+    red, blue = CameraDesc(), CameraDesc()
+    _host_ck(lib().derp_align_derive_cameras(C.byref(a[0]), C.byref(a[1]), C.byref(a[2]), C.byref(a[3]), C.byref(red), C.byref(blue)))
+    out = []
+    for j in (red, blue):
+        cam = dict(green)
+        cam["focal"] = [float(j.focal[0]), float(j.focal[1])]
+        cam.pop("distortion", None)
+        if j.has_distortion:
+            cam["distortion"] = [float(v) for v in j.distortion]
+        out.append(cam)
+    return tuple(out)
 
 
 def mesh_setup_host(vertices, faces, equi_error=True):

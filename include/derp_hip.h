@@ -439,6 +439,31 @@ int derp_sweep_overlap_disparities(int num_depths, uint64_t min_depth_m, uint64_
 int derp_sweep_equirect_depths(int num_depths, double depth_min, double depth_max, float* depths, int* stems);
 int derp_sweep_crop_size(int height, const int* bounds, int* new_width);
 int derp_rig_center(const derp_camera_desc* cams, int n, int index, derp_camera_desc* out_cams);
+/* ---- AlignColors (source/calibration/AlignColors.cpp): the red and blue planes of every camera resampled through
+ * per-channel lens models onto the calibrated (green) rig, ahead of the pyramid ----
+ * The cameras are the destinations of derp_create: the calibrated rig after --cameras, not normalised. Images are
+ * interleaved BGR uint16 at the camera's resolution.
+ * derp_align_derive_cameras: createCalibratedRBRigs for one camera (AlignColors.cpp:72-96). red / blue = `green` with
+ *   scalar focal = the reference channel's times (float)(green focal / reference green focal), {s, -s}, and the reference
+ *   channel's distortion (distortionMax follows, Camera.cpp:119-154). Refuses non-square pixels (getScalarFocal,
+ *   Camera.cpp:185-188). Host only, no context and no device; a refusal leaves its text in derp_last_error(NULL).
+ * derp_align_setup: the three reference rigs must hold exactly one camera each (AlignColors.cpp:164-166, checked here
+ *   and not per frame); derives the models and builds createWarpMap (:52-70) for every camera of the context's rig, red
+ *   and blue, once.
+ * derp_align_maps: one camera's maps, each [h][w][2] float (x, y), as cv::Point2f holds them.
+ * derp_align_frame: warpImage (:98-117) of one frame of every camera: out.G = in.G, out.R = getPixelBilinear(in, red
+ *   map).R, out.B = getPixelBilinear(in, blue map).B (CvUtil.h:108-120, truncating u16 blend). img_w / img_h: the images'
+ *   sizes, which must be the cameras' resolutions. in and out must not overlap.
+ * Two points the reference leaves undefined: a pixel centre exactly on the principal point (0 / 0 there) maps to itself,
+ * the limit of the expression, so its R and B are its own texel's; and undistort's abort when Newton "went past a
+ * maximum" (Camera.h:278) does not exist here: the iteration's value is used. */
+int derp_align_derive_cameras(const derp_camera_desc* green, const derp_camera_desc* red_ref,
+                              const derp_camera_desc* green_ref, const derp_camera_desc* blue_ref,
+                              derp_camera_desc* red, derp_camera_desc* blue);
+int derp_align_setup(derp_ctx* ctx, const derp_camera_desc* red_ref, int n_red, const derp_camera_desc* green_ref,
+                     int n_green, const derp_camera_desc* blue_ref, int n_blue);
+int derp_align_maps(derp_ctx* ctx, int cam, float* red_xy, float* blue_xy);
+int derp_align_frame(derp_ctx* ctx, const uint16_t* const* bgr, const int* img_w, const int* img_h, uint16_t* const* out);
 /* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
  * range, a negative budget, more than 2^31 - 1 vertices or faces).
  * derp_mesh_setup_host: computeInitialQuadrics over plain arrays: vertices f64 [nv][3], faces i32 [nf][3] -> the three
