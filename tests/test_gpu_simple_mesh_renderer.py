@@ -118,6 +118,7 @@ def test_background_compositing(scene):
     eq[..., 3] = 1
     got = g.render_format("eqrcolor", p, background_equirect=eq)
     assert not np.isnan(got).any()
+    assert smr_check.float_equal(got, smr_check.background_equirect(fore, eq)) == 0  # the reference's texel, by value
     g.close()
 
 
@@ -269,7 +270,9 @@ def test_cli_all_formats(built, tmp_path):
     assert smr_check.float_equal(got, smr_check.alpha_blend(fore, backf)[..., :3]) == 0
     imageio.write_png16(str(tmp_path / "eq.png"), back[:16])
     cli(str(tmp_path / "bge"), "--format=eqrcolor", "--file_type=exr", "--background_equirect=" + str(tmp_path / "eq.png"))
-    assert not np.isnan(imageio.read_exr(str(tmp_path / "bge" / "000000.exr"))).any()
+    got = imageio.read_exr(str(tmp_path / "bge" / "000000.exr"))
+    assert not np.isnan(got).any()
+    assert smr_check.float_equal(got, smr_check.background_equirect(fore, backf[:16])[..., :3]) == 0
     # --cameras: only cam1 is loaded and rendered
     cli(str(tmp_path / "one"), "--format=eqrcolor", "--file_type=exr", "--cameras=cam1")
     g1 = derp.Derp([rig["cameras"][1]])

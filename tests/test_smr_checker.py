@@ -1,6 +1,12 @@
 """SimpleMeshRenderer's CPU checker (tests/native/smr_checker.cpp) on its own, without a GPU: configured as the
 rephotography renderer it is the oracle's CanopyScene::cubemap bit for bit; its seamless cube -> equirect blends only
-the faces a direction touches; and the C-ABI reports the output size of every --format."""
+the faces a direction touches; and the C-ABI reports the output size of every --format.
+
+The checker's statistics (chk_render_stats: triangles and won pixels per bounding-box class, displacements, id ties,
+near drops, alpha discards) also stand for oracle_canopy.h's cubemap, which has no counters of its own: configured as
+the rephotography renderer the checker walks the same triangles in the same order with the same depth key and discard,
+and its image is the oracle's bit for bit (below, and for every canopy case of tests/render_cases.py in
+tests/test_render_cases.py), so every pixel has the same winner and every counter the same value."""
 import numpy as np
 import pytest
 
@@ -34,6 +40,28 @@ def test_checker_is_the_rephotography_renderer(built, scene):
         got = smr_check.render(rig["cameras"], disps, cols, include=include, kind="cube", height=24, position=centre,
                                weight="minor", zero_nans=True)
         assert smr_check.float_equal(got, want) == 0
+
+
+def test_statistics(built, scene):
+    """the counters of one render: optional, without effect on the image, summed over the canopies and faces"""
+    rig, colors, disps = scene
+    cols = [np.concatenate([c.astype(np.float32) / 65535, np.ones(c.shape[:2] + (1,), np.float32)], axis=2) for c in colors]
+    args = dict(kind="cube", height=16, position=rig["cameras"][0]["origin"])
+    plain = smr_check.render(rig["cameras"], disps, cols, **args)
+    total, parts = {}, [{} for _ in range(4)]
+    assert smr_check.float_equal(smr_check.render(rig["cameras"], disps, cols, stats=total, **args), plain) == 0
+    assert set(total) == set(smr_check.STATS)
+    for s in range(4):
+        smr_check.render(rig["cameras"], disps, cols, include=[int(k == s) for k in range(4)], stats=parts[s], **args)
+    for key in smr_check.STATS:
+        assert total[key] == sum(p[key] for p in parts), key
+    # 48 x 48 meshes into 16-pixel faces: sub-pixel triangles but for the slab's stretched border; the NaN hole
+    # drops triangles without counting them as near drops
+    assert total["tri_small"] > 1000 and total["pix_small"] >= (~np.isnan(plain[..., 3])).sum() > 0
+    assert total["near_drops"] > 0 and total["suspect"] == 0 and total["mip_above0"] > 0
+    whole = {}
+    smr_check.render(rig["cameras"], [np.full_like(d, np.nan) for d in disps], cols, stats=whole, **args)
+    assert not any(whole.values())
 
 
 def test_checker_weights_and_nans(built, scene):
