@@ -23,11 +23,13 @@ struct Cam {  // normalised camera (resolution 1x1) unless rescaled by the calle
   double dist_max;
   double cos_fov;
   double edge_sq;       // |cameraToSensor((0, sinFov, -cosFov))|^2, for isOutsideImageCircle
+  double cone_kappa;    // cos_fov * (1 + 2^-20): the sure-accept slope of the cost kernels' FOV-cone test (sees<LEAN>)
   int32_t type;
   int32_t default_fov;  // isDefaultFov()
   int32_t dist_zero;    // getDistortion().isZero()
-  int32_t pad;
+  int32_t cone_kind;    // which FOV test cos_fov asks for (kCone*), for the cost kernels' wave-uniform dispatch
 };
+enum { kConeNone = 0, kConeHalfSpace = 1, kConeNarrow = 2, kConeWide = 3 };  // cos_fov == -1, == 0, >= 2^-100, the rest
 
 struct D2 {
   double x, y;
@@ -323,6 +325,13 @@ DERP_HD bool outside_image_circle(const Cam& c, double px, double py, double prx
   return sx * sx + sy * sy >= c.edge_sq;
 }
 
+// Camera.h:154-164 on dot = forward().dot(v) as `sees` computes it: outside the FOV cone (neither the full sphere nor the
+// half space, which `sees` handles itself)
+DERP_HD bool outside_cone(const Cam& c, const D3& v, double dot) {
+  const double sq = sum3(v.x * v.x, v.y * v.y, v.z * v.z);
+  return dot * fabs(dot) <= c.cos_fov * fabs(c.cos_fov) * sq;
+}
+
 // Camera.h:184-190 (+154-164, 121-128, 180-182). Returns false if the point is outside the
 // FOV cone or projects off the sensor; pix in units of (principal, focal, res).
 template <int LEAN = 0>
@@ -332,18 +341,63 @@ DERP_HD bool sees(const Cam& c, const D3& rig, double prx, double pry, double fx
   // backward().dot(v): also the camera-space z used below. forward().dot(v) is its exact negation
   // (negating every product and the sums commutes with round-to-nearest), so it is not recomputed.
   const double back = sum3(c.R[6] * v.x, c.R[7] * v.y, c.R[8] * v.z);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (LEAN & 3) {
+    // The cost kernels' form of the test below. The camera is wave-uniform and the branches go by cone_kind: scalar integer
+    // compares instead of fp64 compares of cos_fov on the vector pipe, twice per projection.
+    if (c.cone_kind == kConeHalfSpace) {
+      if (back >= 0) {
+        return false;
+      }
+    } else if (c.cone_kind == kConeWide) {
+      if (outside_cone(c, v, -back)) {
+        return false;
+      }
+    } else if (c.cone_kind == kConeNarrow) {
+      // 2^-100 <= cos_fov: two lemmas settle nearly every lane without the squared length. Both speak of the COMPUTED dot,
+      // which the reference's expression (outside_cone) uses too. With c = cos_fov, u = 2^-53 and, in exact arithmetic,
+      // X = c^2 (v.x^2 + v.y^2 + v.z^2):
+      //  reject: dot <= 0 (-0 too) gives dot * |dot| <= +0, and the reference's right-hand side, a square times a sum of
+      //          squares, is >= +0 (or NaN, but only if v holds a NaN, and then dot is NaN and fails dot <= 0): the
+      //          reference returns false. No margin, no domain.
+      //  accept: dot > t, t = cone_kappa * (|v.x| + (|v.y| + |v.z|)), cone_kappa = fl(c (1 + 2^-20)). t carries four
+      //          roundings (cone_kappa, two adds, the product), each at most a factor 1 - u below, and |v|_1 >= |v|_2, so
+      //          dot^2 > X (1 + 2^-20)^2 (1 - u)^8 > X (1 + 2^-19). The reference compares fl(dot * |dot|) >= dot^2 (1 - u)
+      //          with fl(fl(c * |c|) * sq) <= X (1 + u)^5 (sq = a0 + (a1 + a2) of three squares nests three roundings deep,
+      //          then c * |c| and the product; an underflow only lowers the value), and (1 + 2^-19)(1 - u) > (1 + u)^5: the
+      //          reference does not return false. Domain: 2^-400 <= |v|_1 < 2^500, so that neither t nor dot * |dot|
+      //          underflows (t >= 2^-501, dot^2 > 2^-1002) and no square overflows. A point of the cost kernels lies a
+      //          float depth (0, or 2^-150 .. 2^128 m) along a pixel's ray from a camera: v is 0 (dot = 0: rejected) or
+      //          inside the domain. An infinite or NaN dot fails the comparison and takes the reference's expression.
+      // The lanes in between, 0 < dot <= t, evaluate the reference's expression unchanged: the sliver of relative width
+      // 2^-20 on the cone, and for a small cos_fov what lies between the cone and dot = cos_fov |v|_1 (|v|_1 is up to
+      // sqrt(3) |v|_2). A wave without such a lane never issues it. One compare serves both the wave's test and the lanes'
+      // mask (a bool and its negation would be two compares: dot may be NaN).
+      const double dot = -back;
+      if (dot <= 0) {
+        return false;
+      }
+      const double t = c.cone_kappa * (fabs(v.x) + (fabs(v.y) + fabs(v.z)));
+      const unsigned long long sure = __builtin_amdgcn_fcmp(dot, t, 2);  // ordered >, the mask of the active lanes
+      const unsigned long long unsure = __builtin_amdgcn_ballot_w64(true) & ~sure;
+      if (unsure != 0ull) {
+        if (__builtin_amdgcn_inverse_ballot_w64(unsure)) {
+          if (outside_cone(c, v, dot)) {
+            return false;
+          }
+        }
+      }
+    }
+  } else
+#endif
   if (c.cos_fov != -1) {
     if (c.cos_fov == 0) {
       // isBehind: backward().dot(v) >= 0
       if (back >= 0) {
         return false;
       }
-    } else {
-      const double dot = -back;
-      const double sq = sum3(v.x * v.x, v.y * v.y, v.z * v.z);
-      if (dot * fabs(dot) <= c.cos_fov * fabs(c.cos_fov) * sq) {
-        return false;
-      }
+    } else if (outside_cone(c, v, -back)) {
+      return false;
     }
   }
   const D3 cam = {
@@ -582,7 +636,9 @@ inline const char* host_prepare_camera(const derp_camera_desc& j, Cam& c) {
     const D2 e = camera_to_sensor(c, D3{0, sin_fov, -c.cos_fov});
     c.edge_sq = e.x * e.x + e.y * e.y;
   }
-  c.pad = 0;
+  c.cone_kappa = c.cos_fov * (1.0 + 0x1.0p-20);
+  // (a positive cos_fov below 2^-100 takes the general test, see `sees`; cos(pi / 2) in double is 2^-54)
+  c.cone_kind = c.cos_fov == -1 ? kConeNone : c.cos_fov == 0 ? kConeHalfSpace : c.cos_fov >= 0x1.0p-100 ? kConeNarrow : kConeWide;
   return nullptr;
 }
 

@@ -1252,6 +1252,13 @@ int derp_set_pyramid(derp_ctx* c, int num_levels, const int* widths, const int* 
   if (num_levels <= 0 || num_levels > kMaxLevels) {
     return fail(c, "num_levels %d out of range (1..%d)", num_levels, kMaxLevels);
   }
+  // the cost kernels round tap positions with a form that holds below 2^23 (round_half_away_pos: a padded side below 2^22
+  // leaves room to spare). No other check bounds a single side.
+  for (int l = 0; l < num_levels; ++l) {
+    if (widths[l] >= (1 << 22) || heights[l] >= (1 << 22)) {
+      return fail(c, "level %d is too large (%dx%d, a side may be 4194303 at most)", l, widths[l], heights[l]);
+    }
+  }
   HIPCHK(c, hipSetDevice(c->device));
   c->numLevels = num_levels;
   c->widthFull = width_full;

@@ -57,7 +57,7 @@ int derp_debug_fp64(derp_ctx* c, int op, const double* a, const double* b, doubl
 }
 
 int derp_debug_expf(derp_ctx* c, int mode, const float* x, float* out, size_t n) {
-  if (!c || !x || !out || mode < 0 || mode > 1) {
+  if (!c || !x || !out || mode < 0 || mode > 2) {  // (2: the cost core's round_half_away_pos)
     return fail(c, "bad arguments");
   }
   if (n == 0) {

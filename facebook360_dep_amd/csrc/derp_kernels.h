@@ -315,6 +315,26 @@ __device__ __forceinline__ void cost_tile_prologue(const LevelView& V, int d, in
   __syncthreads();
 }
 
+// roundf for the cost core's tap positions in two instructions: trunc(x + pred(0.5)), pred(0.5) = 0x1.fffffep-2f the float
+// just below one half, the sum one round-to-nearest fp32 add. Equal to roundf(x) (half away from zero) for every x in
+// (-0.5, 2^23): below 0.5 the sum stays under 1; from 0.5 up to 2^23 the sum is x + 0.5 rounded, and the rounding never
+// crosses an integer that x + 0.5 has not reached (all 1.26e9 floats of [0, 2^23) compared on the host, and
+// tests/test_round_half_away.py; k_debug_expf mode 2 runs it on the device). On (-0.5, 0) both forms give a zero whose
+// sign reaches neither (int)xf nor x - xf + 0.5f. NOT at x = -0.5 (roundf -1, this -0), nor below; 2^23 is where the check stopped.
+// NaN in gives NaN out. (roundf itself expands to trunc, sub, compare, select, bfi, add: six VALU instructions.)
+// The callers' arguments lie in the domain:
+//  - compute_cost's sx, sy: `sees` returned 0 <= pix < 1 for the lanes whose value is used, so sx = (float)(pix * W) is in
+//    [0, W], and derp_set_pyramid keeps W, H < 2^22;
+//  - computeSSD's xDstSrc, yDstSrc: wx + 0.5f with wx a bilerp of projWarp entries, which are (float)(p - 0.5) of a pixel
+//    0 <= p < W that `sees` accepted (k_proj_warp) — at least -0.5 — under weights in [0, 1] that sum to 1 within a few
+//    ulps: wx > -0.75, the sum above -0.25. NaN entries are never stored (compute_cost's consume()).
+// Every cost kernel (random proposals, ping-pong, brute force, the cost map) rounds through this one helper: ping-pong's
+// memoised candidate 0 is random proposals' cost, bit for bit. The !exact path of ssd_arith keeps roundf (x - 1 can be
+// -1.5), and so does everything outside the cost core.
+__device__ __forceinline__ float round_half_away_pos(float x) {
+  return __builtin_truncf(x + 0x1.fffffep-2f);
+}
+
 // The texels one computeSSD call reads, requested ahead of the arithmetic: the 4x4 block of projColor
 // around round(x, y) (rows yi-2..yi+1, cols xi-2..xi+1) and the 2x2 bias taps, as ten 16-byte loads. The
 // block lies inside the padded table for every x, y the tables can produce, and only the rare path at the
@@ -331,7 +351,7 @@ __device__ __forceinline__ void ssd_issue_random(const LevelView& V, const ushor
                                                  const ushort4* __restrict__ bia, float xDstSrc, float yDstSrc, SsdTexels& T,
                                                  bool& border) {
   const int pitch = V.W + 2 * kPadC;
-  const int xi = (int)roundf(xDstSrc), yi = (int)roundf(yDstSrc);
+  const int xi = (int)round_half_away_pos(xDstSrc), yi = (int)round_half_away_pos(yDstSrc);
   const unsigned off = ((unsigned)(yi - 2 + kPadC) * (unsigned)pitch + (unsigned)(xi - 2 + kPadC)) * 8u;
   if constexpr (TILED) {
     const unsigned xa = (unsigned)(xi - 2 + kPadC), ya = (unsigned)(yi - 2 + kPadC);
@@ -378,7 +398,7 @@ __device__ __forceinline__ void ssd_issue_random(const LevelView& V, const ushor
 __device__ __forceinline__ void ssd_issue(const LevelView& V, const ushort4* __restrict__ col,
                                           const ushort4* __restrict__ bia, float xDstSrc, float yDstSrc, SsdTexels& T) {
   const int pitch = V.W + 2 * kPadC;
-  const int xi = (int)roundf(xDstSrc), yi = (int)roundf(yDstSrc);
+  const int xi = (int)round_half_away_pos(xDstSrc), yi = (int)round_half_away_pos(yDstSrc);
   // one table plane is far below 4 GB: 32-bit byte offsets from the (wave-uniform) plane base let the
   // loads use the scalar-base + 32-bit-offset addressing form instead of 64-bit pointer arithmetic
   const unsigned off = ((unsigned)(yi - 2 + kPadC) * (unsigned)pitch + (unsigned)(xi - 2 + kPadC)) * 8u;
@@ -409,7 +429,7 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   auto word_r = [&](const u4a8 (&q)[4][2], int r, int k) { return (k & 1) ? q[r][k >> 1].w : q[r][k >> 1].y; };
   // --- srcBias = getPixelBilinear(dstSrcColorBias, xDstSrc, yDstSrc)
   float bias[3];
-  const float bxf = roundf(xDstSrc), byf = roundf(yDstSrc);
+  const float bxf = round_half_away_pos(xDstSrc), byf = round_half_away_pos(yDstSrc);
   const float bxw = xDstSrc - bxf + 0.5f, byw = yDstSrc - byf + 0.5f;
   const float w00 = (1 - bxw) * (1 - byw), w01 = bxw * (1 - byw), w10 = (1 - bxw) * byw, w11 = bxw * byw;
   if constexpr (RANDOM) {
@@ -618,7 +638,7 @@ __device__ __forceinline__ SsdPair ssd_arith(const LevelView& V, const PixCtx& p
   // the three weights are the same float (x + dx - round(x + dx) is exact by Sterbenz's lemma and equal
   // to x - round(x)): one rounding and one weight serve the three offsets. That holds except on the
   // first texel column / row and where x + 1 crosses into a binade that drops x's last bit.
-  const float xfc = roundf(xDstSrc), yfc = roundf(yDstSrc);
+  const float xfc = round_half_away_pos(xDstSrc), yfc = round_half_away_pos(yDstSrc);
   const bool exact = (xDstSrc >= 1.0f) && (yDstSrc >= 1.0f) && ((xDstSrc + 1.0f) - 1.0f == xDstSrc) &&
                      ((yDstSrc + 1.0f) - 1.0f == yDstSrc);
   int xi[3], yi[3];
@@ -876,7 +896,7 @@ __device__ __forceinline__ float2 compute_cost(const LevelView& V, int dl, int o
         // and is what the allocator spills first)
         const float sx = (float)(pn.x * V.Wd), sy = (float)(pn.y * V.Hd);
         // pDstSrc = getPixelBilinear(dstProjWarp, pSrc)
-        const float xf = roundf(sx), yf = roundf(sy);
+        const float xf = round_half_away_pos(sx), yf = round_half_away_pos(sy);
         const int xi = (int)xf, yi = (int)yf;
         pxw = sx - xf + 0.5f;
         pyw = sy - yf + 0.5f;
@@ -2588,7 +2608,7 @@ __global__ void __launch_bounds__(256) k_debug_expf(int mode, const float* __res
   }
   __syncthreads();
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    out[i] = mode == 0 ? expf_glibc(x[i], expTab) : expf_glibc_nonpos(x[i], expTab);
+    out[i] = mode == 2 ? round_half_away_pos(x[i]) : mode == 0 ? expf_glibc(x[i], expTab) : expf_glibc_nonpos(x[i], expTab);
   }
 }
 

@@ -14,7 +14,7 @@ struct SweepCam {  // one camera's float BGRA image inside the shared buffer
 };
 
 constexpr int kSweepBlock = 256;  // threads per block (four waves), one per pixel
-constexpr int kSweepChunk = 16;   // cameras resident in LDS at a time (Cam + SweepCam: 256 bytes each)
+constexpr int kSweepChunk = 16;   // cameras resident in LDS at a time (Cam + SweepCam: 264 bytes each)
 constexpr int kSweepMaxSplit = 16;  // parts of the depth list (gridDim.z) at most: a run keeps its rays for several depths
 
 enum { kSweepFloat = 0, kSweepU8 = 1 };

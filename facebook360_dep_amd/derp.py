@@ -433,6 +433,13 @@ class Derp:
         self._ck(lib().derp_debug_expf(self.h, int(bool(nonpos)), _p(x), _p(out), C.c_size_t(x.size)))
         return out
 
+    def debug_round_half_away(self, x):
+        """The cost kernels' roundf (round_half_away_pos) on the device, element by element."""
+        x = np.ascontiguousarray(x, np.float32)
+        out = np.zeros_like(x)
+        self._ck(lib().derp_debug_expf(self.h, 2, _p(x), _p(out), C.c_size_t(x.size)))
+        return out
+
     def debug_sees(self, src, xyz):
         """Camera::sees of source camera `src` as the cost kernels evaluate it -> (vis [2, n] bool, pix [2, n, 2] f64):
         row 0 the ping-pong / brute-force variant, row 1 the random-proposal variant (NaN pixels outside the FOV cone)."""

@@ -206,7 +206,8 @@ int derp_debug_fp64(derp_ctx* ctx, int op, const double* a, const double* b, dou
  * for the rig points xyz[3 i .. 3 i + 2]; pix is NaN where the point lies outside the FOV cone */
 int derp_debug_sees(derp_ctx* ctx, int src, const double* xyz, size_t n, double* out);
 /* the filters' expf on the device: out[i] = mode 0 the full routine, 1 the form with the single range test that the joint
- * bilateral filter's fast tap uses, which equals the full one for x[i] in [-inf, -0] */
+ * bilateral filter's fast tap uses, which equals the full one for x[i] in [-inf, -0]; 2 not expf at all but the cost
+ * kernels' two-instruction roundf (round_half_away_pos), which equals roundf for x[i] in (-0.5, 2^23) */
 int derp_debug_expf(derp_ctx* ctx, int mode, const float* x, float* out, size_t n);
 
 /* developer builds (-DDERP_BLOCK_TRACE=1, tools/block_trace.py): {start, end} in 10 ns ticks of every block of the last
