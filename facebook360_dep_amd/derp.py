@@ -60,6 +60,31 @@ class RenderParams(C.Structure):
     ]
 
 
+ISP_MAX_ROLLOFF = 16
+
+
+class IspConfig(C.Structure):
+    """derp_isp_config (include/derp_hip.h)."""
+    _fields_ = [
+        ("bits_per_pixel", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("is_little_endian", C.c_int32),
+        ("is_row_major", C.c_int32), ("bayer_pattern", C.c_char * 8), ("plane_order", C.c_char * 8),
+        ("black_level", C.c_float * 3), ("clamp_min", C.c_float * 3), ("clamp_max", C.c_float * 3),
+        ("stuck_pixel_threshold", C.c_int32), ("stuck_pixel_darkness_threshold", C.c_float),
+        ("stuck_pixel_radius", C.c_int32), ("n_rolloff_h", C.c_int32), ("n_rolloff_v", C.c_int32),
+        ("rolloff_h", (C.c_float * 3) * ISP_MAX_ROLLOFF), ("rolloff_v", (C.c_float * 3) * ISP_MAX_ROLLOFF),
+        ("white_balance_gain", C.c_float * 3), ("ccm", C.c_float * 9), ("saturation", C.c_float), ("gamma", C.c_float * 3),
+        ("low_key_boost", C.c_float * 3), ("high_key_boost", C.c_float * 3), ("contrast", C.c_float),
+        ("sharpening", C.c_float * 3), ("sharpening_support", C.c_float), ("noise_core", C.c_float),
+        ("n_companding_lut", C.c_int32),
+    ]
+
+
+class SimParams(C.Structure):
+    """derp_sim_params (include/derp_hip.h)."""
+    _fields_ = [("ceiling_position", C.c_double), ("ceiling_width", C.c_double), ("ceiling_depth", C.c_double),
+                ("marble_scale", C.c_double), ("marble", C.c_int32), ("pad", C.c_int32)]
+
+
 RENDER_KINDS = {"cube": 0, "equirect": 1, "snapshot": 2}
 WEIGHTS = {"svd": 0, "minor": 1}
 FORMATS = ["cubecolor", "cubedisp", "eqrcolor", "eqrdisp", "lr180", "snapcolor", "snapdisp", "tb3dof", "tbstereo"]
@@ -92,50 +117,205 @@ def render_format_size(fmt, width, height):
     return w.value, h.value
 
 
-# every symbol include/derp_hip.h declares (checked by tests/test_abi.py)
-EXPORTS = [
-    "derp_options_default", "derp_create", "derp_destroy", "derp_last_error", "derp_set_options", "derp_set_pyramid",
-    "derp_build_pyramid_color", "derp_build_pyramid_foreground_mask", "derp_build_pyramid_background_disparity",
-    "derp_download_level_color", "derp_download_level_mask", "derp_download_level_background", "derp_resize_area",
-    "derp_generate_foreground_mask", "derp_image_info", "derp_image_decode", "derp_image_last_error", "derp_jpeg_encode",
-    "derp_upload_color", "derp_upload_foreground_mask", "derp_upload_background_disparity", "derp_upload_disparity",
-    "derp_process_level", "derp_process_pyramid", "derp_synchronize", "derp_download_disparity", "derp_download_cost",
-    "derp_level_begin", "derp_stage_reproject_colors", "derp_stage_brute_force", "derp_stage_random_proposals",
-    "derp_stage_ping_pong", "derp_stage_mismatches", "derp_stage_bilateral_filter", "derp_stage_median_filter", "derp_stage_mask_fov",
-    "derp_level_end", "derp_set_level_disparity", "derp_get_level_disparity", "derp_cost_map", "derp_debug_download",
-    "derp_debug_atan2_ypos", "derp_debug_fp64", "derp_debug_sees", "derp_debug_expf", "derp_debug_block_trace",
-    "derp_ssim", "derp_average_score", "derp_rephotograph", "derp_rephotograph_upload", "derp_rephotograph_render", "derp_canopy_cubemap",
-    "derp_render_params_default", "derp_render_upload", "derp_render", "derp_render_format_size", "derp_render_format",
-    "derp_render_vertices",
-    "derp_export_points", "derp_points_begin", "derp_points_splat", "derp_points_download", "derp_project_equirect_mask",
-    "derp_mesh_build", "derp_mesh_counts", "derp_mesh_setup", "derp_mesh_simplify", "derp_mesh_download_f64", "derp_mesh_download",
-    "derp_mesh_simplify_parallel", "derp_mesh_parallel_pass",
-    "derp_mesh_setup_host", "derp_mesh_simplify_host",
-    "derp_fov_mask", "derp_layer_disparities", "derp_download_mismatch_mask", "derp_upsample_disparity", "derp_joint_bilateral_u16", "derp_joint_bilateral_f32", "derp_masked_median",
-    "derp_temporal_filter", "derp_temporal_filter_dev", "derp_dev_disparity", "derp_dev_color", "derp_dev_mask",
-    "derp_get_counters", "derp_reset_counters", "derp_profile_enable", "derp_profile_reset", "derp_profile_query", "derp_profile_memoised",
-    "derp_device_name", "derp_device_memory", "derp_host_nth_element_pairs", "derp_host_minstd_uniform", "derp_host_cost_tile_map",
-    "derp_set_frame_slots", "derp_select_frame", "derp_frame_slots", "derp_host_alloc", "derp_host_free", "derp_bind_thread", "derp_host_register", "derp_host_unregister",
-    "derp_seq_options_default", "derp_seq_window", "derp_seq_owner", "derp_seq_plan", "derp_seq_create", "derp_seq_destroy",
-    "derp_seq_counts", "derp_seq_frames", "derp_seq_frame_slot", "derp_seq_buffer", "derp_rccl_unique_id",
-    "derp_seq_attach_rccl", "derp_seq_attach_loopback", "derp_seq_attach_external", "derp_seq_selftest",
-    "derp_seq_exchange_inputs", "derp_seq_level_compute", "derp_seq_level_exchange", "derp_seq_level_filter",
-    "derp_seq_host_inputs", "derp_seq_buffer_copy", "derp_seq_upload_color_plane", "derp_seq_upload_disparity", "derp_seq_download_disparity", "derp_seq_exchange_inputs_level",
-    "derp_seq_level_compute_frame", "derp_seq_level_provided_frame", "derp_seq_mark_exchanged", "derp_seq_level_filter_frame", "derp_seq_download_filtered",
-    "derp_seq_run", "derp_seq_stats", "derp_seq_stats_reset", "derp_seq_exchange_exposed_ms",
-    "derp_isp_config_default", "derp_isp_create", "derp_isp_destroy", "derp_isp_output_size", "derp_isp_process",
-    "derp_isp_stage", "derp_isp_tables",
-    "derp_sim_scene_create", "derp_sim_scene_destroy", "derp_sim_scene_icosahedrons", "derp_sim_scene_cubes",
-    "derp_sim_scene_ground_plane", "derp_sim_scene_add_triangle", "derp_sim_bvh_build", "derp_sim_scene_counts",
-    "derp_sim_scene_get", "derp_sim_perlin_table", "derp_sim_icosahedron", "derp_sim_noise", "derp_sim_trace_host", "derp_sim_create",
-    "derp_sim_destroy", "derp_sim_upload", "derp_sim_render_camera", "derp_sim_render_equirect", "derp_sim_trace_rays",
-    "derp_sim_stage_size", "derp_sim_stage",
-    "derp_gc_upload", "derp_gc_download_image", "derp_gc_slices", "derp_gc_set_clean", "derp_gc_sweep", "derp_gc_clean",
-    "derp_gc_run", "derp_gc_result", "derp_gc_stage", "derp_gc_slice_count",
-    "derp_sweep_upload", "derp_sweep_overlaps", "derp_sweep_equirect_bounds", "derp_sweep_equirect",
-    "derp_sweep_overlap_disparities", "derp_sweep_equirect_depths", "derp_sweep_crop_size", "derp_rig_center",
-    "derp_align_derive_cameras", "derp_align_setup", "derp_align_maps", "derp_align_frame",
-]
+# The prototype of every function include/derp_hip.h declares: name -> (restype, [argtypes]), applied by lib() and held
+# against the header by tests/test_abi.py. int32_t / uint64_t / size_t / float / double by value keep their width;
+# const char* is c_char_p; a pointer to a struct mirrored above is POINTER(mirror); handles and every other pointer are
+# c_void_p (None = NULL).
+_int, _size, _u64, _f32, _f64, _str, _ptr = C.c_int, C.c_size_t, C.c_uint64, C.c_float, C.c_double, C.c_char_p, C.c_void_p
+_cam, _opt, _seq_opt, _transfer = C.POINTER(CameraDesc), C.POINTER(Options), C.POINTER(SeqOptions), C.POINTER(SeqTransfer)
+_pass, _view, _isp, _sim = C.POINTER(MeshPass), C.POINTER(RenderParams), C.POINTER(IspConfig), C.POINTER(SimParams)
+PROTOTYPES = {
+    "derp_options_default": (None, [_opt]),
+    "derp_create": (_int, [_ptr, _int, _cam, _int, _cam, _int]),
+    "derp_destroy": (None, [_ptr]),
+    "derp_last_error": (_str, [_ptr]),
+    "derp_set_options": (_int, [_ptr, _opt]),
+    "derp_set_pyramid": (_int, [_ptr, _int, _ptr, _ptr, _int, _int]),
+    "derp_set_frame_slots": (_int, [_ptr, _int]),
+    "derp_select_frame": (_int, [_ptr, _int]),
+    "derp_frame_slots": (_int, [_ptr, _ptr, _ptr]),
+    "derp_host_alloc": (_ptr, [_size]),
+    "derp_host_free": (None, [_ptr]),
+    "derp_bind_thread": (_int, [_ptr]),
+    "derp_host_register": (_int, [_ptr, _size]),
+    "derp_host_unregister": (None, [_ptr]),
+    "derp_upload_color": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_upload_foreground_mask": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_upload_background_disparity": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_upload_disparity": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_build_pyramid_color": (_int, [_ptr, _int, _ptr, _int, _int]),
+    "derp_build_pyramid_foreground_mask": (_int, [_ptr, _int, _ptr, _int, _int, _int]),
+    "derp_build_pyramid_background_disparity": (_int, [_ptr, _int, _ptr, _int, _int]),
+    "derp_download_level_color": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_download_level_mask": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_download_level_background": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_image_info": (_int, [_ptr, _size, _ptr, _ptr, _ptr, _ptr]),
+    "derp_image_decode": (_int, [_ptr, _size, _ptr, _size]),
+    "derp_image_last_error": (_str, []),
+    "derp_jpeg_encode": (_int, [_ptr, _int, _int, _int, _int, _ptr, _size, _ptr]),
+    "derp_resize_area": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _int, _int]),
+    "derp_generate_foreground_mask": (_int, [_ptr, _ptr, _ptr, _int, _int, _int, _f32, _int, _ptr]),
+    "derp_process_level": (_int, [_ptr, _int]),
+    "derp_process_pyramid": (_int, [_ptr, _int, _int]),
+    "derp_synchronize": (_int, [_ptr]),
+    "derp_download_disparity": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_download_cost": (_int, [_ptr, _int, _ptr, _ptr]),
+    "derp_level_begin": (_int, [_ptr, _int]),
+    "derp_stage_reproject_colors": (_int, [_ptr]),
+    "derp_stage_brute_force": (_int, [_ptr]),
+    "derp_stage_random_proposals": (_int, [_ptr]),
+    "derp_stage_ping_pong": (_int, [_ptr]),
+    "derp_stage_mismatches": (_int, [_ptr]),
+    "derp_stage_bilateral_filter": (_int, [_ptr]),
+    "derp_stage_median_filter": (_int, [_ptr]),
+    "derp_stage_mask_fov": (_int, [_ptr]),
+    "derp_level_end": (_int, [_ptr]),
+    "derp_set_level_disparity": (_int, [_ptr, _int, _ptr]),
+    "derp_get_level_disparity": (_int, [_ptr, _int, _ptr]),
+    "derp_cost_map": (_int, [_ptr, _int, _ptr, _ptr, _ptr]),
+    "derp_debug_download": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_debug_atan2_ypos": (_int, [_ptr, _ptr, _ptr, _ptr, _size]),
+    "derp_debug_fp64": (_int, [_ptr, _int, _ptr, _ptr, _ptr, _size]),
+    "derp_debug_sees": (_int, [_ptr, _int, _ptr, _size, _ptr]),
+    "derp_debug_expf": (_int, [_ptr, _int, _ptr, _ptr, _size]),
+    "derp_debug_block_trace": (_int, [_ptr, _str, _int, _ptr, _size, _ptr, _ptr]),
+    "derp_download_mismatch_mask": (_int, [_ptr, _int, _ptr]),
+    "derp_layer_disparities": (_int, [_ptr, _ptr, _ptr, _size, _ptr]),
+    "derp_ssim": (_int, [_ptr, _ptr, _ptr, _int, _int, _int, _f32, _f32, _f32, _ptr]),
+    "derp_average_score": (_int, [_ptr, _ptr, _int, _int, _ptr]),
+    "derp_rephotograph": (_int, [_ptr, _int, _ptr, _ptr, _int, _int, _ptr]),
+    "derp_rephotograph_upload": (_int, [_ptr, _ptr, _ptr, _int, _int]),
+    "derp_rephotograph_render": (_int, [_ptr, _int, _ptr]),
+    "derp_canopy_cubemap": (_int, [_ptr, _ptr, _ptr, _int, _ptr]),
+    "derp_render_params_default": (None, [_view]),
+    "derp_render_upload": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_render": (_int, [_ptr, _view, _ptr, _ptr]),
+    "derp_render_format_size": (_int, [_str, _int, _int, _ptr, _ptr]),
+    "derp_render_format": (_int, [_ptr, _str, _view, _ptr, _ptr, _int, _int, _ptr]),
+    "derp_render_vertices": (_int, [_ptr, _int, _f32, _ptr]),
+    "derp_export_points": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _f64, _int, _int, _ptr, _size, _ptr]),
+    "derp_points_begin": (_int, [_ptr, _ptr, _ptr]),
+    "derp_points_splat": (_int, [_ptr, _ptr, _size, _f64, _f64]),
+    "derp_points_download": (_int, [_ptr, _int, _ptr]),
+    "derp_project_equirect_mask": (_int, [_ptr, _int, _ptr, _int, _int, _int, _int, _f64, _ptr]),
+    "derp_mesh_build": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _f64, _ptr, _int, _int, _f32]),
+    "derp_mesh_counts": (_int, [_ptr, _ptr, _ptr, _ptr]),
+    "derp_mesh_setup": (_int, [_ptr, _int, _ptr, _ptr, _ptr]),
+    "derp_mesh_simplify": (_int, [_ptr, _int, _f32, _int, _int, _int, _ptr]),
+    "derp_mesh_simplify_parallel": (_int, [_ptr, _int, _f32, _int, _int, _ptr]),
+    "derp_mesh_parallel_pass": (_int, [_ptr, _int, _pass]),
+    "derp_mesh_download_f64": (_int, [_ptr, _ptr, _ptr]),
+    "derp_mesh_download": (_int, [_ptr, _int, _ptr, _ptr]),
+    "derp_gc_upload": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_gc_download_image": (_int, [_ptr, _int, _ptr]),
+    "derp_gc_slices": (_int, [_ptr, _int, _f64, _ptr, _ptr, _int]),
+    "derp_gc_slice_count": (_int, [_cam, _int, _int, _int, _int, _f64, _ptr]),
+    "derp_gc_set_clean": (_int, [_ptr, _ptr]),
+    "derp_gc_sweep": (_int, [_ptr, _int, _f64, _int, _f64, _int, _ptr]),
+    "derp_gc_clean": (_int, [_ptr, _ptr, _ptr, _ptr, _f64, _ptr]),
+    "derp_gc_run": (_int, [_ptr, _f64, _f64, _int, _int]),
+    "derp_gc_result": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_gc_stage": (_int, [_ptr, _int, _int, _int, _f64, _int, _f64, _ptr, _ptr, _ptr, _ptr]),
+    "derp_sweep_upload": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_sweep_overlaps": (_int, [_ptr, _int, _ptr, _int, _int, _ptr]),
+    "derp_sweep_equirect_bounds": (_int, [_ptr, _int, _int, _f32, _ptr]),
+    "derp_sweep_equirect": (_int, [_ptr, _int, _int, _ptr, _int, _int, _ptr, _int, _ptr, _int, _ptr]),
+    "derp_sweep_overlap_disparities": (_int, [_int, _u64, _u64, _ptr, _ptr]),
+    "derp_sweep_equirect_depths": (_int, [_int, _f64, _f64, _ptr, _ptr]),
+    "derp_sweep_crop_size": (_int, [_int, _ptr, _ptr]),
+    "derp_rig_center": (_int, [_cam, _int, _int, _cam]),
+    "derp_align_derive_cameras": (_int, [_cam, _cam, _cam, _cam, _cam, _cam]),
+    "derp_align_setup": (_int, [_ptr, _cam, _int, _cam, _int, _cam, _int]),
+    "derp_align_maps": (_int, [_ptr, _int, _ptr, _ptr]),
+    "derp_align_frame": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_mesh_setup_host": (_int, [_ptr, _size, _ptr, _size, _int, _ptr, _ptr, _ptr]),
+    "derp_mesh_simplify_host": (_int, [_ptr, _size, _ptr, _size, _ptr, _ptr, _ptr, _int, _f32, _int, _int, _ptr, _ptr, _ptr,
+                                      _ptr, _ptr]),
+    "derp_fov_mask": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_upsample_disparity": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _ptr, _ptr, _int, _int, _int, _ptr]),
+    "derp_joint_bilateral_u16": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _f32, _f32, _f32, _f32, _ptr]),
+    "derp_joint_bilateral_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _f32, _f32, _f32, _f32, _ptr]),
+    "derp_masked_median": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _ptr]),
+    "derp_temporal_filter": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _int, _f32, _int, _f32, _f32, _f32, _ptr]),
+    "derp_temporal_filter_dev": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _int, _f32, _int, _f32, _f32, _f32, _ptr]),
+    "derp_dev_disparity": (_int, [_ptr, _int, _int, _ptr, _ptr]),
+    "derp_dev_color": (_int, [_ptr, _int, _int, _ptr, _ptr]),
+    "derp_dev_mask": (_int, [_ptr, _int, _int, _ptr, _ptr]),
+    "derp_seq_options_default": (None, [_seq_opt]),
+    "derp_seq_window": (None, [_int, _int, _int, _int, _ptr, _ptr]),
+    "derp_seq_owner": (_int, [_int, _int, _int, _int, _int]),
+    "derp_seq_plan": (_int, [_int, _int, _int, _int, _int, _transfer, _int]),
+    "derp_seq_create": (_int, [_ptr, _ptr, _int, _int, _int, _int, _seq_opt]),
+    "derp_seq_destroy": (None, [_ptr]),
+    "derp_seq_counts": (_int, [_ptr, _ptr, _ptr]),
+    "derp_seq_frames": (_int, [_ptr, _int, _ptr, _int]),
+    "derp_seq_frame_slot": (_int, [_ptr, _int]),
+    "derp_seq_host_inputs": (_int, [_ptr, _int, _int, _ptr, _ptr, _ptr]),
+    "derp_seq_upload_color_plane": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_seq_upload_disparity": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_seq_download_disparity": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_seq_buffer": (_int, [_ptr, _int, _int, _int, _ptr, _ptr]),
+    "derp_seq_buffer_copy": (_int, [_ptr, _int, _int, _int, _ptr, _size, _int]),
+    "derp_rccl_unique_id": (_int, [_ptr, _size]),
+    "derp_seq_attach_rccl": (_int, [_ptr, _ptr, _size]),
+    "derp_seq_attach_loopback": (_int, [_ptr, _ptr, _int]),
+    "derp_seq_attach_external": (_int, [_ptr]),
+    "derp_seq_selftest": (_int, [_ptr, _int]),
+    "derp_seq_exchange_inputs": (_int, [_ptr]),
+    "derp_seq_exchange_inputs_level": (_int, [_ptr, _int]),
+    "derp_seq_level_compute": (_int, [_ptr, _int]),
+    "derp_seq_level_compute_frame": (_int, [_ptr, _int, _int]),
+    "derp_seq_level_provided_frame": (_int, [_ptr, _int, _int]),
+    "derp_seq_level_exchange": (_int, [_ptr, _int]),
+    "derp_seq_mark_exchanged": (_int, [_ptr, _int]),
+    "derp_seq_level_filter": (_int, [_ptr, _int]),
+    "derp_seq_level_filter_frame": (_int, [_ptr, _int, _int]),
+    "derp_seq_download_filtered": (_int, [_ptr, _int, _int, _int, _ptr]),
+    "derp_seq_run": (_int, [_ptr, _int, _int]),
+    "derp_seq_stats": (_int, [_ptr, _ptr, _ptr, _ptr]),
+    "derp_seq_stats_reset": (_int, [_ptr]),
+    "derp_seq_exchange_exposed_ms": (_int, [_ptr, _ptr]),
+    "derp_isp_config_default": (None, [_isp]),
+    "derp_isp_create": (_int, [_ptr, _int, _isp, _int, _int, _int]),
+    "derp_isp_destroy": (None, [_ptr]),
+    "derp_isp_output_size": (_int, [_ptr, _ptr, _ptr]),
+    "derp_isp_process": (_int, [_ptr, _ptr, _size, _ptr]),
+    "derp_isp_stage": (_int, [_ptr, _int, _ptr]),
+    "derp_isp_tables": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_sim_scene_create": (_ptr, []),
+    "derp_sim_scene_destroy": (None, [_ptr]),
+    "derp_sim_scene_icosahedrons": (_int, [_ptr, _int, _f64, _f64, _f64, _f64, _int]),
+    "derp_sim_scene_cubes": (_int, [_ptr]),
+    "derp_sim_scene_ground_plane": (_int, [_ptr, _f64]),
+    "derp_sim_scene_add_triangle": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
+    "derp_sim_bvh_build": (_int, [_ptr, _int, _int, _int]),
+    "derp_sim_scene_counts": (_int, [_ptr, _ptr, _ptr, _ptr]),
+    "derp_sim_scene_get": (_int, [_ptr, _ptr, _ptr, _ptr]),
+    "derp_sim_perlin_table": (None, [_ptr]),
+    "derp_sim_icosahedron": (None, [_ptr, _ptr]),
+    "derp_sim_noise": (_int, [_ptr, _int, _int, _f64]),
+    "derp_sim_trace_host": (_int, [_ptr, _ptr, _size, _ptr]),
+    "derp_sim_create": (_int, [_ptr, _int]),
+    "derp_sim_destroy": (None, [_ptr]),
+    "derp_sim_upload": (_int, [_ptr, _ptr, _int, _ptr, _int, _ptr, _int, _ptr, _int, _int, _ptr, _int, _int, _sim]),
+    "derp_sim_render_camera": (_int, [_ptr, _cam, _int, _ptr, _ptr]),
+    "derp_sim_render_equirect": (_int, [_ptr, _int, _int, _int, _int, _f64, _ptr, _ptr, _ptr]),
+    "derp_sim_trace_rays": (_int, [_ptr, _ptr, _size]),
+    "derp_sim_stage_size": (_int, [_ptr, _ptr, _ptr]),
+    "derp_sim_stage": (_int, [_ptr, _int, _int, _ptr]),
+    "derp_get_counters": (_int, [_ptr, _ptr, _ptr, _ptr]),
+    "derp_reset_counters": (_int, [_ptr]),
+    "derp_profile_enable": (_int, [_ptr, _int]),
+    "derp_profile_reset": (_int, [_ptr]),
+    "derp_profile_query": (_int, [_ptr, _str, _int, _ptr, _ptr, _ptr, _ptr]),
+    "derp_profile_memoised": (_int, [_ptr, _str, _int, _ptr]),
+    "derp_device_name": (_int, [_ptr, _str, _int]),
+    "derp_device_memory": (_int, [_ptr, _ptr, _ptr]),
+    "derp_host_nth_element_pairs": (_int, [_ptr, _int, _int]),
+    "derp_host_minstd_uniform": (_f32, [_int, _u64, _f32, _f32]),
+    "derp_host_cost_tile_map": (_int, [_int, _int, _int, _int, _ptr, _int]),
+}
+EXPORTS = list(PROTOTYPES)  # every symbol include/derp_hip.h declares
 
 _lib = None
 
@@ -156,13 +336,9 @@ def lib():
         except ImportError:
             pass
         _lib = C.CDLL(LIB_PATH)
-        _lib.derp_last_error.restype = C.c_char_p
-        _lib.derp_last_error.argtypes = [C.c_void_p]
-        _lib.derp_host_minstd_uniform.restype = C.c_float
-        _lib.derp_host_minstd_uniform.argtypes = [C.c_int, C.c_uint64, C.c_float, C.c_float]
-        _lib.derp_sim_scene_create.restype = C.c_void_p
-        _lib.derp_sim_scene_destroy.argtypes = [C.c_void_p]
-        _lib.derp_sim_scene_destroy.restype = None
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return _lib
 
 
@@ -201,6 +377,15 @@ def filter_destinations(cams, destinations):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _ptrs(arrays):
+    """T* const*: the arrays' addresses (the caller keeps the arrays alive)"""
+    return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+
+def _ints(values):
+    return (C.c_int * len(values))(*values)
 
 
 class DerpError(RuntimeError):
@@ -254,9 +439,8 @@ class Derp:
 
     def set_pyramid(self, sizes, width_full, height_full):
         self.sizes = list(sizes)
-        w = (C.c_int * len(sizes))(*[s[0] for s in sizes])
-        h = (C.c_int * len(sizes))(*[s[1] for s in sizes])
-        self._ck(lib().derp_set_pyramid(self.h, len(sizes), w, h, width_full, height_full))
+        self._ck(lib().derp_set_pyramid(self.h, len(sizes), _ints([s[0] for s in sizes]), _ints([s[1] for s in sizes]),
+                                        width_full, height_full))
 
     def _shape(self, level):
         w, h = self.sizes[level]
@@ -325,7 +509,7 @@ class Derp:
         h, w = frame.shape[:2]
         out = np.zeros((h, w), dtype=np.uint8)
         self._ck(lib().derp_generate_foreground_mask(self.h, _p(template), _p(frame), w, h, blur_radius,
-                                                     C.c_float(threshold), morph_closing_size, _p(out)))
+                                                     threshold, morph_closing_size, _p(out)))
         return out
 
     # ---- frame slots
@@ -411,7 +595,7 @@ class Derp:
         y = np.ascontiguousarray(y, np.float64)
         x = np.ascontiguousarray(x, np.float64)
         out = np.zeros_like(y)
-        self._ck(lib().derp_debug_atan2_ypos(self.h, _p(y), _p(x), _p(out), C.c_size_t(y.size)))
+        self._ck(lib().derp_debug_atan2_ypos(self.h, _p(y), _p(x), _p(out), y.size))
         return out
 
     FP64_OPS = {"sqrt_lean": 0, "sqrt": 1, "div_plain": 2, "div": 3}
@@ -422,7 +606,7 @@ class Derp:
         b = None if b is None else np.ascontiguousarray(b, np.float64)
         assert b is None or b.shape == a.shape
         out = np.zeros_like(a)
-        self._ck(lib().derp_debug_fp64(self.h, self.FP64_OPS[op], _p(a), _p(b), _p(out), C.c_size_t(a.size)))
+        self._ck(lib().derp_debug_fp64(self.h, self.FP64_OPS[op], _p(a), _p(b), _p(out), a.size))
         return out
 
     def debug_expf(self, x, nonpos=False):
@@ -430,14 +614,14 @@ class Derp:
         test that stands in for it on arguments in [-inf, -0]."""
         x = np.ascontiguousarray(x, np.float32)
         out = np.zeros_like(x)
-        self._ck(lib().derp_debug_expf(self.h, int(bool(nonpos)), _p(x), _p(out), C.c_size_t(x.size)))
+        self._ck(lib().derp_debug_expf(self.h, int(bool(nonpos)), _p(x), _p(out), x.size))
         return out
 
     def debug_round_half_away(self, x):
         """The cost kernels' roundf (round_half_away_pos) on the device, element by element."""
         x = np.ascontiguousarray(x, np.float32)
         out = np.zeros_like(x)
-        self._ck(lib().derp_debug_expf(self.h, 2, _p(x), _p(out), C.c_size_t(x.size)))
+        self._ck(lib().derp_debug_expf(self.h, 2, _p(x), _p(out), x.size))
         return out
 
     def debug_sees(self, src, xyz):
@@ -445,7 +629,7 @@ class Derp:
         row 0 the ping-pong / brute-force variant, row 1 the random-proposal variant (NaN pixels outside the FOV cone)."""
         xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
         out = np.zeros((len(xyz), 2, 3))
-        self._ck(lib().derp_debug_sees(self.h, src, _p(xyz), C.c_size_t(len(xyz)), _p(out)))
+        self._ck(lib().derp_debug_sees(self.h, src, _p(xyz), len(xyz), _p(out)))
         return out[:, :, 0].T != 0, np.ascontiguousarray(out[:, :, 1:].transpose(1, 0, 2))
 
     def debug(self, d, s, which):
@@ -473,7 +657,7 @@ class Derp:
         fg = np.ascontiguousarray(fg, dtype=np.float32)
         bg = np.ascontiguousarray(bg, dtype=np.float32)
         out = np.zeros(fg.shape, dtype=np.uint8)
-        self._ck(lib().derp_layer_disparities(self.h, _p(fg), _p(bg), C.c_size_t(fg.size), _p(out)))
+        self._ck(lib().derp_layer_disparities(self.h, _p(fg), _p(bg), fg.size, _p(out)))
         return out
 
     # ---- rephotography score (RephotographyUtil.h, ComputeRephotographyErrors.cpp)
@@ -482,8 +666,7 @@ class Derp:
         y = np.ascontiguousarray(y, dtype=np.float32)
         h, w = x.shape[:2]
         out = np.zeros((h, w, 3), dtype=np.float32)
-        self._ck(lib().derp_ssim(self.h, _p(x), _p(y), w, h, blur_radius, C.c_float(alpha), C.c_float(beta),
-                                 C.c_float(gamma), _p(out)))
+        self._ck(lib().derp_ssim(self.h, _p(x), _p(y), w, h, blur_radius, alpha, beta, gamma, _p(out)))
         return out
 
     def rephotograph(self, target, colors, disps):
@@ -491,19 +674,15 @@ class Derp:
         colors = [np.ascontiguousarray(c, dtype=np.uint16) for c in colors]
         disps = [np.ascontiguousarray(d, dtype=np.float32) for d in disps]
         h, w = disps[0].shape
-        cp = (C.c_void_p * len(colors))(*[c.ctypes.data for c in colors])
-        dp = (C.c_void_p * len(disps))(*[d.ctypes.data for d in disps])
         out = np.zeros((h, w, 4), dtype=np.float32)
-        self._ck(lib().derp_rephotograph(self.h, target, cp, dp, w, h, _p(out)))
+        self._ck(lib().derp_rephotograph(self.h, target, _ptrs(colors), _ptrs(disps), w, h, _p(out)))
         return out
 
     def rephotograph_upload(self, colors, disps):
         colors = [np.ascontiguousarray(c, dtype=np.uint16) for c in colors]
         disps = [np.ascontiguousarray(d, dtype=np.float32) for d in disps]
         h, w = disps[0].shape
-        cp = (C.c_void_p * len(colors))(*[c.ctypes.data for c in colors])
-        dp = (C.c_void_p * len(disps))(*[d.ctypes.data for d in disps])
-        self._ck(lib().derp_rephotograph_upload(self.h, cp, dp, w, h))
+        self._ck(lib().derp_rephotograph_upload(self.h, _ptrs(colors), _ptrs(disps), w, h))
 
     def canopy_cubemap(self, include, centre, edge):
         """CanopyScene::cubemap of the uploaded cameras with include[s] != 0, seen from `centre`
@@ -517,18 +696,14 @@ class Derp:
     def render_upload(self, disps, colors=None):
         """SimpleMeshRenderer's scene: disps[s] f32 [h, w], colors[s] float BGRA [h', w', 4] (own sizes) or None."""
         disps = [np.ascontiguousarray(d, dtype=np.float32) for d in disps]
-        dp = (C.c_void_p * len(disps))(*[d.ctypes.data for d in disps])
-        dw = (C.c_int * len(disps))(*[d.shape[1] for d in disps])
-        dh = (C.c_int * len(disps))(*[d.shape[0] for d in disps])
+        dp, dw, dh = _ptrs(disps), _ints([d.shape[1] for d in disps]), _ints([d.shape[0] for d in disps])
         if colors is None:
             self._ck(lib().derp_render_upload(self.h, None, None, None, dp, dw, dh))
             return
         colors = [np.ascontiguousarray(c, dtype=np.float32) for c in colors]
         assert all(c.ndim == 3 and c.shape[2] == 4 for c in colors)
-        cp = (C.c_void_p * len(colors))(*[c.ctypes.data for c in colors])
-        cw = (C.c_int * len(colors))(*[c.shape[1] for c in colors])
-        ch = (C.c_int * len(colors))(*[c.shape[0] for c in colors])
-        self._ck(lib().derp_render_upload(self.h, cp, cw, ch, dp, dw, dh))
+        self._ck(lib().derp_render_upload(self.h, _ptrs(colors), _ints([c.shape[1] for c in colors]),
+                                          _ints([c.shape[0] for c in colors]), dp, dw, dh))
 
     def render(self, params, include=None):
         """derp_render of the uploaded scene -> BGRA f32: cube [6 h, h, 4], equirect [h, 2 h, 4], snapshot [h, w, 4]."""
@@ -554,7 +729,7 @@ class Derp:
     def render_vertices(self, cam, shape, ipd):
         """camera `cam`'s mesh vertices after canopyVS's stereo stage (ipd 0: none) -> f32 [h, w, 4]."""
         out = np.zeros((shape[0], shape[1], 4), dtype=np.float32)
-        self._ck(lib().derp_render_vertices(self.h, cam, C.c_float(ipd), _p(out)))
+        self._ck(lib().derp_render_vertices(self.h, cam, ipd, _p(out)))
         return out
 
     # ---- conversion tools (source/conversion): cameras = this context's destinations, rescaled to the image size
@@ -568,8 +743,8 @@ class Derp:
         cap = h * w if cap is None else cap
         out = np.zeros((cap, 6), dtype=np.float32)
         count = C.c_size_t()
-        rc = lib().derp_export_points(self.h, cam, _p(disparity), w, h, _p(color_bgr), C.c_double(max_depth), int(clip),
-                                      subsample, _p(out), C.c_size_t(cap), C.byref(count))
+        rc = lib().derp_export_points(self.h, cam, _p(disparity), w, h, _p(color_bgr), max_depth, int(clip),
+                                      subsample, _p(out), cap, C.byref(count))
         self.last_point_count = count.value
         self._ck(rc)
         return out[:count.value].copy()
@@ -578,15 +753,12 @@ class Derp:
         """One (w, h) per camera; the disparity images start at zero."""
         assert len(sizes) == self.D
         self._points_sizes = [tuple(s) for s in sizes]
-        w = (C.c_int * self.D)(*[s[0] for s in sizes])
-        h = (C.c_int * self.D)(*[s[1] for s in sizes])
-        self._ck(lib().derp_points_begin(self.h, w, h))
+        self._ck(lib().derp_points_begin(self.h, _ints([s[0] for s in sizes]), _ints([s[1] for s in sizes])))
 
     def points_splat(self, xyz, min_depth=0.0, max_depth=float("inf")):
         """projectPointsToCameras of ImportPointCloud for one chunk of points f64 [n, 3]; chunks accumulate."""
         xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        self._ck(lib().derp_points_splat(self.h, _p(xyz), C.c_size_t(len(xyz)), C.c_double(min_depth),
-                                         C.c_double(max_depth)))
+        self._ck(lib().derp_points_splat(self.h, _p(xyz), len(xyz), min_depth, max_depth))
 
     def points_download(self, cam):
         sizes = getattr(self, "_points_sizes", [])
@@ -599,8 +771,8 @@ class Derp:
         """ProjectEquirectsToCameras for one camera: equirect mask u8 [eh, ew] (non-zero = set) -> u8 {0,1} [h, w]."""
         eqr = np.ascontiguousarray(eqr, dtype=np.uint8)
         out = np.zeros((h, w), dtype=np.uint8)
-        self._ck(lib().derp_project_equirect_mask(self.h, cam, _p(eqr), eqr.shape[1], eqr.shape[0], w, h,
-                                                  C.c_double(depth), _p(out)))
+        self._ck(lib().derp_project_equirect_mask(self.h, cam, _p(eqr), eqr.shape[1], eqr.shape[0], w, h, depth,
+                                                  _p(out)))
         return out
 
     # ---- GeometricConsistency (source/render/GeometricConsistency.cpp): cameras = this context's destinations (the
@@ -617,10 +789,9 @@ class Derp:
                 im = np.concatenate([im, np.full(im.shape[:2] + (1,), 65535, np.uint16)], axis=2)
             full.append(np.ascontiguousarray(im))
         self._gc_sizes = [(int(w), int(h)) for w, h in small_sizes]
-        ptrs = (C.c_void_p * self.D)(*[im.ctypes.data for im in full])
-        ints = lambda v: (C.c_int * self.D)(*v)
-        self._ck(lib().derp_gc_upload(self.h, ptrs, ints([im.shape[1] for im in full]), ints([im.shape[0] for im in full]),
-                                      ints([s[0] for s in self._gc_sizes]), ints([s[1] for s in self._gc_sizes])))
+        self._ck(lib().derp_gc_upload(self.h, _ptrs(full), _ints([im.shape[1] for im in full]),
+                                      _ints([im.shape[0] for im in full]), _ints([s[0] for s in self._gc_sizes]),
+                                      _ints([s[1] for s in self._gc_sizes])))
 
     def _gc_shape(self, cam):
         sizes = getattr(self, "_gc_sizes", [])
@@ -636,9 +807,9 @@ class Derp:
     def gc_slices(self, dst, disparity_step=0.5):
         """-> the slice disparities of `dst`, f32 [sliceCount]"""
         n = C.c_int()
-        self._ck(lib().derp_gc_slices(self.h, dst, C.c_double(disparity_step), C.byref(n), None, 0))
+        self._ck(lib().derp_gc_slices(self.h, dst, disparity_step, C.byref(n), None, 0))
         out = np.zeros(n.value, dtype=np.float32)
-        self._ck(lib().derp_gc_slices(self.h, dst, C.c_double(disparity_step), C.byref(n), _p(out), n.value))
+        self._ck(lib().derp_gc_slices(self.h, dst, disparity_step, C.byref(n), _p(out), n.value))
         return out
 
     def gc_set_clean(self, clean):
@@ -648,13 +819,13 @@ class Derp:
             return
         clean = [np.ascontiguousarray(d, dtype=np.float32) for d in clean]
         assert [d.shape for d in clean] == [self._gc_shape(i) for i in range(self.D)]
-        self._ck(lib().derp_gc_set_clean(self.h, (C.c_void_p * self.D)(*[d.ctypes.data for d in clean])))
+        self._ck(lib().derp_gc_set_clean(self.h, _ptrs(clean)))
 
     def gc_sweep(self, dst, disparity_step=0.5, use_clean=False, agree_fraction=0.75, split=0):
         """computeDepth of one destination -> depth f32 [h, w]"""
         out = np.zeros(self._gc_shape(dst), dtype=np.float32)
-        self._ck(lib().derp_gc_sweep(self.h, dst, C.c_double(disparity_step), int(bool(use_clean)),
-                                     C.c_double(agree_fraction), split, _p(out)))
+        self._ck(lib().derp_gc_sweep(self.h, dst, disparity_step, int(bool(use_clean)), agree_fraction, split,
+                                     _p(out)))
         return out
 
     def gc_clean(self, depths, agree_fraction=0.75):
@@ -662,15 +833,13 @@ class Derp:
         depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
         assert len(depths) == self.D
         outs = [np.zeros_like(d) for d in depths]
-        ints = lambda v: (C.c_int * self.D)(*v)
-        self._ck(lib().derp_gc_clean(self.h, (C.c_void_p * self.D)(*[d.ctypes.data for d in depths]),
-                                     ints([d.shape[1] for d in depths]), ints([d.shape[0] for d in depths]),
-                                     C.c_double(agree_fraction), (C.c_void_p * self.D)(*[o.ctypes.data for o in outs])))
+        self._ck(lib().derp_gc_clean(self.h, _ptrs(depths), _ints([d.shape[1] for d in depths]),
+                                     _ints([d.shape[0] for d in depths]), agree_fraction, _ptrs(outs)))
         return outs
 
     def gc_run(self, disparity_step=0.5, agree_fraction=0.75, pass_count=2, keep_clean=False):
         """processFrame of the uploaded frame; results through gc_result"""
-        self._ck(lib().derp_gc_run(self.h, C.c_double(disparity_step), C.c_double(agree_fraction), pass_count,
+        self._ck(lib().derp_gc_run(self.h, disparity_step, agree_fraction, pass_count,
                                    int(bool(keep_clean))))
 
     def gc_result(self, kind, cam, pass_index=0):
@@ -684,8 +853,8 @@ class Derp:
         shape = self._gc_shape(dst)
         out = {k: np.zeros(shape + (4,), dtype=np.int16) for k in ("sample", "average", "average_of_sq")}
         out["cost"] = np.zeros(shape, dtype=np.float32)
-        self._ck(lib().derp_gc_stage(self.h, dst, src, slice_index, C.c_double(disparity_step), int(bool(use_clean)),
-                                     C.c_double(agree_fraction), _p(out["sample"]), _p(out["average"]),
+        self._ck(lib().derp_gc_stage(self.h, dst, src, slice_index, disparity_step, int(bool(use_clean)),
+                                     agree_fraction, _p(out["sample"]), _p(out["average"]),
                                      _p(out["average_of_sq"]), _p(out["cost"])))
         return out
 
@@ -699,8 +868,7 @@ class Derp:
         res = None if resolution is None else (C.c_double * 2)(float(resolution[0]), float(resolution[1]))
         mask = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         mh, mw = (0, 0) if mask is None else mask.shape
-        self._ck(lib().derp_mesh_build(self.h, cam, _p(disparity), w, h, res, C.c_double(depth_scale), _p(mask), mw, mh,
-                                       C.c_float(tear_ratio)))
+        self._ck(lib().derp_mesh_build(self.h, cam, _p(disparity), w, h, res, depth_scale, _p(mask), mw, mh, tear_ratio))
         return self.mesh_counts()
 
     def mesh_counts(self):
@@ -718,14 +886,14 @@ class Derp:
     def mesh_simplify(self, num_faces_out, strictness=0.2, remove_boundary_edges=False, equi_error=True, host_setup=False):
         """MeshSimplifier::simplify of the built mesh -> (passes of the loop, DERP_MESH_EXIT_*)"""
         stats = (C.c_int * 2)()
-        self._ck(lib().derp_mesh_simplify(self.h, num_faces_out, C.c_float(strictness), int(remove_boundary_edges),
+        self._ck(lib().derp_mesh_simplify(self.h, num_faces_out, strictness, int(remove_boundary_edges),
                                           int(equi_error), int(host_setup), stats))
         return stats[0], stats[1]
 
     def mesh_simplify_parallel(self, num_faces_out, strictness=0.2, remove_boundary_edges=False, equi_error=True):
         """the pass-parallel simplifier of the built mesh, on the device -> (passes, DERP_MESH_EXIT_*)"""
         stats = (C.c_int * 2)()
-        self._ck(lib().derp_mesh_simplify_parallel(self.h, num_faces_out, C.c_float(strictness), int(remove_boundary_edges),
+        self._ck(lib().derp_mesh_simplify_parallel(self.h, num_faces_out, strictness, int(remove_boundary_edges),
                                                    int(equi_error), stats))
         return stats[0], stats[1]
 
@@ -773,8 +941,8 @@ class Derp:
         mask = np.ascontiguousarray(mask, dtype=np.uint8)
         h, w = image.shape
         out = np.zeros_like(image)
-        self._ck(lib().derp_joint_bilateral_u16(self.h, _p(image), _p(guide), _p(mask), w, h, radius, C.c_float(sigma),
-                                                C.c_float(w0), C.c_float(w1), C.c_float(w2), _p(out)))
+        self._ck(lib().derp_joint_bilateral_u16(self.h, _p(image), _p(guide), _p(mask), w, h, radius, sigma, w0, w1, w2,
+                                                _p(out)))
         return out
 
     def joint_bilateral_f32(self, image, guide, mask, radius, sigma, w0, w1, w2):
@@ -783,8 +951,8 @@ class Derp:
         mask = np.ascontiguousarray(mask, dtype=np.uint8)
         h, w = image.shape
         out = np.zeros_like(image)
-        self._ck(lib().derp_joint_bilateral_f32(self.h, _p(image), _p(guide), _p(mask), w, h, radius, C.c_float(sigma),
-                                                C.c_float(w0), C.c_float(w1), C.c_float(w2), _p(out)))
+        self._ck(lib().derp_joint_bilateral_f32(self.h, _p(image), _p(guide), _p(mask), w, h, radius, sigma, w0, w1, w2,
+                                                _p(out)))
         return out
 
     def masked_median(self, image, background, mask, radius=1):
@@ -802,12 +970,9 @@ class Derp:
         images = [np.ascontiguousarray(g, dtype=np.float32) for g in images]
         masks = [np.ascontiguousarray(g, dtype=np.uint8) for g in masks]
         h, w = images[0].shape
-        gp = (C.c_void_p * n)(*[g.ctypes.data for g in guides])
-        ip = (C.c_void_p * n)(*[g.ctypes.data for g in images])
-        mp = (C.c_void_p * n)(*[g.ctypes.data for g in masks])
         out = np.zeros((h, w), dtype=np.float32)
-        self._ck(lib().derp_temporal_filter(self.h, gp, ip, mp, n, w, h, frame_offset, C.c_float(sigma), radius,
-                                            C.c_float(w0), C.c_float(w1), C.c_float(w2), _p(out)))
+        self._ck(lib().derp_temporal_filter(self.h, _ptrs(guides), _ptrs(images), _ptrs(masks), n, w, h, frame_offset,
+                                            sigma, radius, w0, w1, w2, _p(out)))
         return out
 
     def temporal_filter_dev(self, guide_ptrs, disp_ptrs, mask_ptrs, w, h, frame_offset, sigma, radius, w0, w1, w2,
@@ -816,8 +981,8 @@ class Derp:
         gp = (C.c_void_p * n)(*guide_ptrs)
         ip = (C.c_void_p * n)(*disp_ptrs)
         mp = (C.c_void_p * n)(*mask_ptrs)
-        self._ck(lib().derp_temporal_filter_dev(self.h, gp, ip, mp, n, w, h, frame_offset, C.c_float(sigma), radius,
-                                                C.c_float(w0), C.c_float(w1), C.c_float(w2), C.c_void_p(out_ptr)))
+        self._ck(lib().derp_temporal_filter_dev(self.h, gp, ip, mp, n, w, h, frame_offset, sigma, radius, w0, w1, w2,
+                                                out_ptr))
 
     def dev_disparity(self, level, d):
         p, n = C.c_void_p(), C.c_size_t()
@@ -864,9 +1029,9 @@ class Derp:
         """-> uint64 [grid_y, grid_x, 2]: start / end (10 ns ticks) of the blocks of the stage's last launch at `level`
         (a library built with -DDERP_BLOCK_TRACE=1 only)"""
         gx, gy = C.c_int(), C.c_int()
-        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, None, C.c_size_t(0), C.byref(gx), C.byref(gy)))
+        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, None, 0, C.byref(gx), C.byref(gy)))
         out = np.zeros((gy.value, gx.value, 2), dtype=np.uint64)
-        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, _p(out), C.c_size_t(out.size), C.byref(gx), C.byref(gy)))
+        self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, _p(out), out.size, C.byref(gx), C.byref(gy)))
         return out
 
     def device_memory(self):
@@ -882,11 +1047,9 @@ class Derp:
         assert len(images) == self.D and len(resolutions) == self.D
         ims = [np.ascontiguousarray(im, dtype=np.float32) for im in images]
         assert all(im.ndim == 3 and im.shape[2] == 4 for im in ims)
-        ints = lambda v: (C.c_int * self.D)(*[int(x) for x in v])  # noqa: E731
         res = np.ascontiguousarray(np.asarray(resolutions, dtype=np.float64).reshape(self.D, 2))
-        ptrs = (C.c_void_p * self.D)(*[im.ctypes.data for im in ims])
-        self._ck(lib().derp_sweep_upload(self.h, ptrs, ints([im.shape[1] for im in ims]), ints([im.shape[0] for im in ims]),
-                                         _p(res)))
+        self._ck(lib().derp_sweep_upload(self.h, _ptrs(ims), _ints([im.shape[1] for im in ims]),
+                                         _ints([im.shape[0] for im in ims]), _p(res)))
         self._sweep_shapes = [im.shape[:2] for im in ims]
 
     def sweep_overlaps(self, dst, disparities, u8=False):
@@ -902,14 +1065,14 @@ class Derp:
     def sweep_equirect_bounds(self, width, height, depth):
         """-> (minX, maxX, minY, maxY) of the columns and rows at which any camera sees the equirect's point"""
         b = (C.c_int * 4)()
-        self._ck(lib().derp_sweep_equirect_bounds(self.h, int(width), int(height), C.c_float(depth), b))
+        self._ck(lib().derp_sweep_equirect_bounds(self.h, int(width), int(height), depth, b))
         return tuple(b)
 
     def sweep_equirect(self, width, height, depths, window=None, out_size=None, black_bg=False, u8=False):
         """window: None or (minX, maxX, minY, maxY) with out_size = (w, h) -> [n, h, w, 4] float32 or uint8"""
         d = np.ascontiguousarray(depths, dtype=np.float32).reshape(-1)
         ow, oh = (width, height) if out_size is None else out_size
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        win = None if window is None else _ints([int(v) for v in window])
         bg = (C.c_float * 4)(0, 0, 0 if black_bg else 1, 1)
         out = np.zeros((len(d), int(oh), int(ow), 4), dtype=np.uint8 if u8 else np.float32)
         self._ck(lib().derp_sweep_equirect(self.h, int(width), int(height), win, int(ow), int(oh), _p(d), len(d), bg,
@@ -941,10 +1104,8 @@ class Derp:
         ims = [np.ascontiguousarray(im, dtype=np.uint16) for im in images]
         assert all(im.ndim == 3 and im.shape[2] == 3 for im in ims)
         outs = [np.zeros_like(im) for im in ims]
-        ints = lambda v: (C.c_int * self.D)(*[int(x) for x in v])  # noqa: E731
-        src = (C.c_void_p * self.D)(*[im.ctypes.data for im in ims])
-        dst = (C.c_void_p * self.D)(*[o.ctypes.data for o in outs])
-        self._ck(lib().derp_align_frame(self.h, src, ints([im.shape[1] for im in ims]), ints([im.shape[0] for im in ims]), dst))
+        self._ck(lib().derp_align_frame(self.h, _ptrs(ims), _ints([im.shape[1] for im in ims]),
+                                        _ints([im.shape[0] for im in ims]), _ptrs(outs)))
         return outs
 
     def device_name(self):
@@ -961,7 +1122,7 @@ def gc_slice_count(cams, dst, small_size, disparity_step=0.5):
     size (w, h), on the host (no device); raises DerpError with the refusal's text."""
     a = (CameraDesc * len(cams))(*[camera_desc(c) for c in cams])
     n = C.c_int()
-    if lib().derp_gc_slice_count(a, len(cams), dst, int(small_size[0]), int(small_size[1]), C.c_double(disparity_step),
+    if lib().derp_gc_slice_count(a, len(cams), dst, int(small_size[0]), int(small_size[1]), disparity_step,
                                  C.byref(n)):
         raise DerpError(lib().derp_last_error(None).decode())
     return n.value
@@ -975,21 +1136,21 @@ def _host_ck(rc):
 def sweep_overlap_disparities(num_depths, min_depth_m=1, max_depth_m=10):
     """GenerateCameraOverlaps' disparities in sweep order and their files' stems (int(depth * 100)), on the host"""
     d, s = np.zeros(max(num_depths, 0), dtype=np.float32), np.zeros(max(num_depths, 0), dtype=np.int32)
-    _host_ck(lib().derp_sweep_overlap_disparities(int(num_depths), C.c_uint64(min_depth_m), C.c_uint64(max_depth_m), _p(d), _p(s)))
+    _host_ck(lib().derp_sweep_overlap_disparities(int(num_depths), min_depth_m, max_depth_m, _p(d), _p(s)))
     return d, s
 
 
 def sweep_equirect_depths(num_depths, depth_min=1.0, depth_max=10.0):
     """GenerateEquirect's depths by index and their files' stems, on the host"""
     d, s = np.zeros(max(num_depths, 0), dtype=np.float32), np.zeros(max(num_depths, 0), dtype=np.int32)
-    _host_ck(lib().derp_sweep_equirect_depths(int(num_depths), C.c_double(depth_min), C.c_double(depth_max), _p(d), _p(s)))
+    _host_ck(lib().derp_sweep_equirect_depths(int(num_depths), depth_min, depth_max, _p(d), _p(s)))
     return d, s
 
 
 def sweep_crop_size(height, bounds):
     """--crop_equirect's width for the bounds (minX, maxX, minY, maxY); raises DerpError on an empty box"""
     w = C.c_int()
-    _host_ck(lib().derp_sweep_crop_size(int(height), (C.c_int * 4)(*[int(v) for v in bounds]), C.byref(w)))
+    _host_ck(lib().derp_sweep_crop_size(int(height), _ints([int(v) for v in bounds]), C.byref(w)))
     return w.value
 
 
@@ -1030,7 +1191,7 @@ def mesh_setup_host(vertices, faces, equi_error=True):
     v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
     f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
     planes, costs, vq = np.zeros((len(f), 4)), np.zeros((len(f), 3)), np.zeros((len(v), 10))
-    if lib().derp_mesh_setup_host(_p(v), C.c_size_t(len(v)), _p(f), C.c_size_t(len(f)), int(equi_error), _p(planes),
+    if lib().derp_mesh_setup_host(_p(v), len(v), _p(f), len(f), int(equi_error), _p(planes),
                                   _p(costs), _p(vq)):
         raise DerpError("derp_mesh_setup_host: bad arguments")
     return planes, costs, vq
@@ -1046,8 +1207,8 @@ def mesh_simplify_host(vertices, faces, num_faces_out, strictness=0.2, remove_bo
     ov, of = np.zeros_like(v), np.zeros_like(f)
     nv, nf = C.c_size_t(), C.c_size_t()
     stats = (C.c_int * 2)()
-    if lib().derp_mesh_simplify_host(_p(v), C.c_size_t(len(v)), _p(f), C.c_size_t(len(f)), _p(planes), _p(costs), _p(vq),
-                                     num_faces_out, C.c_float(strictness), int(remove_boundary_edges), int(equi_error),
+    if lib().derp_mesh_simplify_host(_p(v), len(v), _p(f), len(f), _p(planes), _p(costs), _p(vq),
+                                     num_faces_out, strictness, int(remove_boundary_edges), int(equi_error),
                                      _p(ov), _p(of), C.byref(nv), C.byref(nf), stats):
         raise DerpError("derp_mesh_simplify_host: bad arguments")
     return ov[:nv.value].copy(), of[:nf.value].copy(), (stats[0], stats[1])
@@ -1060,7 +1221,7 @@ def host_nth_element_pairs(pairs, nth):
 
 
 def host_minstd_uniform(seed, draw_index, a, b):
-    return lib().derp_host_minstd_uniform(seed, draw_index, C.c_float(a), C.c_float(b))
+    return lib().derp_host_minstd_uniform(seed, draw_index, a, b)
 
 
 def host_cost_tile_map(tiles, bands, rot, per_block):
@@ -1090,25 +1251,8 @@ def format_results(avg):
 
 
 # ---------------------------------------------------------------- camera ISP (raw Bayer -> RGB)
-ISP_MAX_ROLLOFF = 16
 ISP_FILTERS = {"bilinear": 0, "frequency": 1, "edge_aware": 2, "chroma_suppressed_bilinear": 3}
 ISP_STAGES = ["load", "pixel", "stuck", "demosaic", "color", "lowpass", "sharpened"]
-
-
-class IspConfig(C.Structure):
-    """derp_isp_config (include/derp_hip.h)."""
-    _fields_ = [
-        ("bits_per_pixel", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("is_little_endian", C.c_int32),
-        ("is_row_major", C.c_int32), ("bayer_pattern", C.c_char * 8), ("plane_order", C.c_char * 8),
-        ("black_level", C.c_float * 3), ("clamp_min", C.c_float * 3), ("clamp_max", C.c_float * 3),
-        ("stuck_pixel_threshold", C.c_int32), ("stuck_pixel_darkness_threshold", C.c_float),
-        ("stuck_pixel_radius", C.c_int32), ("n_rolloff_h", C.c_int32), ("n_rolloff_v", C.c_int32),
-        ("rolloff_h", (C.c_float * 3) * ISP_MAX_ROLLOFF), ("rolloff_v", (C.c_float * 3) * ISP_MAX_ROLLOFF),
-        ("white_balance_gain", C.c_float * 3), ("ccm", C.c_float * 9), ("saturation", C.c_float), ("gamma", C.c_float * 3),
-        ("low_key_boost", C.c_float * 3), ("high_key_boost", C.c_float * 3), ("contrast", C.c_float),
-        ("sharpening", C.c_float * 3), ("sharpening_support", C.c_float), ("noise_core", C.c_float),
-        ("n_companding_lut", C.c_int32),
-    ]
 
 
 def isp_config(config):
@@ -1188,7 +1332,7 @@ class Isp:
         """raw: the .raw file's bytes (or an array of them) -> [h, w, 3] BGR, u8 or u16 like the sensor"""
         buf = np.frombuffer(raw, dtype=np.uint8) if isinstance(raw, (bytes, bytearray)) else np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
         out = np.zeros((self.height, self.width, 3), self.dtype)
-        self._ck(lib().derp_isp_process(self.h, _p(buf), C.c_size_t(buf.size), _p(out)))
+        self._ck(lib().derp_isp_process(self.h, _p(buf), buf.size, _p(out)))
         return out
 
     def stage(self, stage):
@@ -1215,12 +1359,6 @@ SIM_STAGES = {"origin": (0, np.float32, 3), "direction": (1, np.float32, 3), "hi
               "distance": (3, np.float32, 1), "color": (4, np.float32, 3)}
 
 
-class SimParams(C.Structure):
-    """derp_sim_params (include/derp_hip.h)."""
-    _fields_ = [("ceiling_position", C.c_double), ("ceiling_width", C.c_double), ("ceiling_depth", C.c_double),
-                ("marble_scale", C.c_double), ("marble", C.c_int32), ("pad", C.c_int32)]
-
-
 class SimScene:
     """RigSimulator's triangles and sphere tree, built on the host (no device): the builders append, build_bvh()
     flattens. The random builders draw from the C library's rand(): srand() first for a repeatable scene."""
@@ -1242,8 +1380,8 @@ class SimScene:
             raise DerpError("derp_sim_scene: bad arguments")
 
     def icosahedrons(self, count=250, min_dist=100.0, max_dist=250.0, min_radius=20.0, max_radius=50.0, red_triangle=False):
-        self._ck(lib().derp_sim_scene_icosahedrons(self.h, int(count), C.c_double(min_dist), C.c_double(max_dist),
-                                                   C.c_double(min_radius), C.c_double(max_radius), int(bool(red_triangle))))
+        self._ck(lib().derp_sim_scene_icosahedrons(self.h, int(count), min_dist, max_dist, min_radius, max_radius,
+                                                   int(bool(red_triangle))))
         return self
 
     def cubes(self):
@@ -1251,7 +1389,7 @@ class SimScene:
         return self
 
     def ground_plane(self, dist=1.70):
-        self._ck(lib().derp_sim_scene_ground_plane(self.h, C.c_double(dist)))
+        self._ck(lib().derp_sim_scene_ground_plane(self.h, dist))
         return self
 
     def add_triangle(self, v0, v1, v2, color_bgr):
@@ -1275,14 +1413,14 @@ class SimScene:
         """Single-thread CPU tracer (geometry only): rays [n, 6] -> [n, 4] (b, g, r, depth)."""
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
         out = np.zeros((rays.shape[0], 4), np.float32)
-        self._ck(lib().derp_sim_trace_host(self.h, _p(rays), C.c_size_t(rays.shape[0]), _p(out)))
+        self._ck(lib().derp_sim_trace_host(self.h, _p(rays), rays.shape[0], _p(out)))
         return out
 
 
 def sim_noise(bgr, amplitude):
     """corruptImageWithNoise in place on a float32 [h, w, 3] image (rand() of the C library)."""
     assert bgr.dtype == np.float32 and bgr.flags.c_contiguous and bgr.ndim == 3 and bgr.shape[2] == 3
-    if lib().derp_sim_noise(_p(bgr), bgr.shape[1], bgr.shape[0], C.c_double(amplitude)):
+    if lib().derp_sim_noise(_p(bgr), bgr.shape[1], bgr.shape[0], amplitude):
         raise DerpError("derp_sim_noise: bad arguments")
     return bgr
 
@@ -1344,13 +1482,13 @@ class Sim:
         """mono: (bgr, inverse depth); stereo: (left, right)."""
         a = np.zeros((h, w, 3), np.float32)
         b = np.zeros((h, w, 3), np.float32) if stereo else np.zeros((h, w), np.float32)
-        self._ck(lib().derp_sim_render_equirect(self.h, w, h, int(aas), int(bool(stereo)), C.c_double(interpupillary_radius),
+        self._ck(lib().derp_sim_render_equirect(self.h, w, h, int(aas), int(bool(stereo)), interpupillary_radius,
                                                 _p(a), _p(b) if stereo else None, None if stereo else _p(b)))
         return a, b
 
     def trace_rays(self, rays):
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
-        self._ck(lib().derp_sim_trace_rays(self.h, _p(rays), C.c_size_t(rays.shape[0])))
+        self._ck(lib().derp_sim_trace_rays(self.h, _p(rays), rays.shape[0]))
 
     def stage(self, name, eye=0):
         """A supersampled plane of the last render: origin, direction, hit, distance, color."""

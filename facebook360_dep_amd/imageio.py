@@ -195,14 +195,13 @@ def read_image(path):
     from . import derp
 
     lib = derp.lib()
-    lib.derp_image_last_error.restype = C.c_char_p
     with open(path, "rb") as f:
         data = f.read()
     w, h, ch, bd = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    if lib.derp_image_info(data, C.c_size_t(len(data)), C.byref(w), C.byref(h), C.byref(ch), C.byref(bd)):
+    if lib.derp_image_info(data, len(data), C.byref(w), C.byref(h), C.byref(ch), C.byref(bd)):
         raise ValueError("failed to load image: %s (%s)" % (path, lib.derp_image_last_error().decode()))
     out = np.empty((h.value, w.value, ch.value), dtype=np.float32 if bd.value == 32 else np.uint16)
-    if lib.derp_image_decode(data, C.c_size_t(len(data)), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)):
+    if lib.derp_image_decode(data, len(data), out.ctypes.data_as(C.c_void_p), out.nbytes):
         raise ValueError("failed to load image: %s (%s)" % (path, lib.derp_image_last_error().decode()))
     if bd.value == 8:
         out = out.astype(np.uint8)
@@ -220,13 +219,12 @@ def write_jpeg(path, arr, quality=95):
     if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
         raise ValueError("JPEG holds 8-bit gray or 3-channel images")
     lib = derp.lib()
-    lib.derp_image_last_error.restype = C.c_char_p
     h, w = a.shape[:2]
     ch = 1 if a.ndim == 2 else 3
     size = C.c_size_t(0)
     cap = w * h * ch * 4 + 4096  # a coefficient costs at most a 16-bit code + 11 bits: under four bytes per sample
     buf = (C.c_ubyte * cap)()
-    if lib.derp_jpeg_encode(a.ctypes.data_as(C.c_void_p), w, h, ch, int(quality), buf, C.c_size_t(cap), C.byref(size)):
+    if lib.derp_jpeg_encode(a.ctypes.data_as(C.c_void_p), w, h, ch, int(quality), buf, cap, C.byref(size)):
         raise ValueError("failed to save image: %s (%s)" % (path, lib.derp_image_last_error().decode()))
     with open(path, "wb") as f:
         f.write(memoryview(buf)[: size.value])

@@ -210,10 +210,7 @@ class SequenceRunner:
                 bg = np.ascontiguousarray(np.stack([arr(data["bg_disp"][level][g._dst_src(d)]) for d in range(g.D)]),
                                           np.float32)
             keep.append((col, fg, bg))
-            self._ck(derp.lib().derp_seq_host_inputs(
-                self.h, frame, level, col.ctypes.data_as(C.c_void_p),
-                fg.ctypes.data_as(C.c_void_p) if fg is not None else None,
-                bg.ctypes.data_as(C.c_void_p) if bg is not None else None))
+            self._ck(derp.lib().derp_seq_host_inputs(self.h, frame, level, derp._p(col), derp._p(fg), derp._p(bg)))
         self._host[frame] = keep
 
     def download_disparity(self, frame, level, d):
@@ -221,7 +218,7 @@ class SequenceRunner:
 
         w, h = self.g.sizes[level]
         out = np.zeros((h, w), dtype=np.float32)
-        self._ck(derp.lib().derp_seq_download_disparity(self.h, frame, level, d, out.ctypes.data_as(C.c_void_p)))
+        self._ck(derp.lib().derp_seq_download_disparity(self.h, frame, level, d, derp._p(out)))
         return out
 
     def result_crc(self, level=0):
@@ -395,7 +392,7 @@ class SequenceRunner:
 
         w, h = self.g.sizes[level]
         out = np.zeros((h, w), dtype=np.float32)
-        self._ck(derp.lib().derp_seq_download_filtered(self.h, frame, level, d, out.ctypes.data_as(C.c_void_p)))
+        self._ck(derp.lib().derp_seq_download_filtered(self.h, frame, level, d, derp._p(out)))
         return out
 
     def before_exchange(self):
