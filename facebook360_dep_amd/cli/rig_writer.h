@@ -39,11 +39,23 @@ struct JsonOut {
     }
     out += '"';
   }
+  // digits <= 0 (saveRig's default, folly's shortest form): the fewest significant digits that read back as the same
+  // double, with ".0" after a whole number so that it stays a double for every reader
+  static std::string shortest(double v) {
+    std::string s;
+    for (int p = 1; p <= 17; ++p) {
+      s = fmt("%.*g", p, v);
+      if (std::strtod(s.c_str(), nullptr) == v) {
+        break;
+      }
+    }
+    return s.find_first_of(".eni") == std::string::npos ? s + ".0" : s;
+  }
   void write(std::string& out, int digits, int indent = 0) const {
     const std::string pad((size_t)indent + 2, ' '), close((size_t)indent, ' ');
     switch (kind) {
       case Int: out += std::to_string(i); break;
-      case Dbl: out += fmt("%.*f", digits, d); break;
+      case Dbl: out += digits > 0 ? fmt("%.*f", digits, d) : shortest(d); break;
       case Bool: out += b ? "true" : "false"; break;
       case Str: quote(s, out); break;
       case Arr:
@@ -92,7 +104,8 @@ static void write_text(const fs::path& path, const std::string& text) {
 // written for a rig that passes its isUnitary check). The optional "group" is not part of the C-ABI's camera: it is
 // read from the rig file a second time (rig_groups) and handed in by camera id.
 static void save_rig(const fs::path& path, const std::vector<derp_camera_desc>& rig,
-                     const std::map<std::string, std::string>& groups, int digits) {
+                     const std::map<std::string, std::string>& groups, int digits,
+                     const std::vector<std::string>& comments = {}) {
   static const char* kTypes[] = {"FTHETA", "RECTILINEAR", "EQUISOLID", "ORTHOGRAPHIC"};
   JsonOut root = JsonOut::object();
   JsonOut cams = JsonOut::array();
@@ -128,6 +141,13 @@ static void save_rig(const fs::path& path, const std::vector<derp_camera_desc>& 
     cams.arr.push_back(j);
   }
   root.obj["cameras"] = cams;
+  if (!comments.empty()) {
+    JsonOut list = JsonOut::array();
+    for (const std::string& line : comments) {
+      list.arr.push_back(JsonOut::string(line));
+    }
+    root.obj["comments"] = list;
+  }
   std::string text;
   root.write(text, digits);
   write_text(path, text + "\n");

@@ -28,6 +28,7 @@
 #include "derp_geometric.h"
 #include "derp_sweep.h"
 #include "derp_align.h"
+#include "derp_coverage.h"
 
 using namespace derp;
 
@@ -1633,6 +1634,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
 #include "derp_mesh_api.h"
 #include "derp_geometric_api.h"
 #include "derp_sweep_api.h"
+#include "derp_coverage_api.h"
 #include "derp_align_api.h"
 #include "derp_filters_api.h"
 #include "derp_debug_api.h"

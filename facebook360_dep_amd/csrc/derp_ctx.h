@@ -29,13 +29,14 @@ enum Stage {
   ST_SWEEP_EQUIRECT,
   ST_ALIGN_MAPS,  // AlignColors (derp_align_api.h), timed under level 0
   ST_ALIGN_COLORS,
+  ST_COVERAGE,  // RigAnalyzer (derp_coverage_api.h), timed under level 0
   ST_COUNT
 };
 const char* kStageNames[ST_COUNT] = {"fov_mask",  "variance",    "own_bias",         "upsample",  "proj_warp",
                                      "reproject", "proj_bias",   "brute_force",      "random_proposals",
                                      "ping_pong", "mismatches",  "bilateral",        "median",    "mask_fov",
                                      "temporal",  "lanes_wall", "gc_prepare",       "gc_sweep",  "gc_clean",
-                                     "sweep_overlaps", "sweep_equirect", "align_maps",       "align_colors"};
+                                     "sweep_overlaps", "sweep_equirect", "align_maps",       "align_colors", "coverage"};
 constexpr int kMaxLevels = 24;
 
 struct TimedSpan {
@@ -83,7 +84,7 @@ struct WorkLane {
 };
 
 // per tool family, defined in its derp_*_api.h and created by the family's first call that needs it
-struct SmrState; struct RephotoState; struct PointsState; struct MeshState; struct GcState; struct SweepState; struct AlignState;
+struct SmrState; struct RephotoState; struct PointsState; struct MeshState; struct GcState; struct SweepState; struct AlignState; struct CoverageState;
 
 }  // namespace
 
@@ -185,6 +186,7 @@ struct derp_ctx {
   std::unique_ptr<GcState> gc;
   std::unique_ptr<SweepState> sweep;
   std::unique_ptr<AlignState> align;
+  std::unique_ptr<CoverageState> coverage;
 };
 
 namespace {

@@ -224,6 +224,20 @@ PROTOTYPES = {
     "derp_sweep_equirect_depths": (_int, [_int, _f64, _f64, _ptr, _ptr]),
     "derp_sweep_crop_size": (_int, [_int, _ptr, _ptr]),
     "derp_rig_center": (_int, [_cam, _int, _int, _cam]),
+    "derp_coverage_directions": (_int, [_ptr, _ptr, _int, _ptr, _int, _ptr, _ptr]),
+    "derp_coverage_equirect": (_int, [_ptr, _int, _f64, _ptr, _ptr, _ptr]),
+    "derp_coverage_camera": (_int, [_ptr, _int, _f64, _ptr]),
+    "derp_coverage_cross_section": (_int, [_ptr, _int, _ptr]),
+    "derp_rig_fibonacci_units": (_int, [_int, _f64, _ptr, _ptr]),
+    "derp_rig_coverage_distances": (_int, [_f64, _ptr]),
+    "derp_rig_euler_matrix": (_int, [_ptr, _int, _ptr]),
+    "derp_rig_align_z_matrix": (_int, [_ptr, _ptr]),
+    "derp_rig_from_eulers": (_int, [_cam, _ptr, _int, _int, _cam]),
+    "derp_rig_arrangement": (_int, [_str, _cam, _f64, _cam, _ptr]),
+    "derp_rig_revolve": (_int, [_cam, _int, _ptr, _int, _cam]),
+    "derp_rig_rotate": (_int, [_cam, _int, _ptr, _cam]),
+    "derp_rig_perturb": (_int, [_cam, _int, _int, _f64, _f64, _f64, _f64]),
+    "derp_rig_scale": (_int, [_cam, _int, _f64, _f64, _f64]),
     "derp_align_derive_cameras": (_int, [_cam, _cam, _cam, _cam, _cam, _cam]),
     "derp_align_setup": (_int, [_ptr, _cam, _int, _cam, _int, _cam, _int]),
     "derp_align_maps": (_int, [_ptr, _int, _ptr, _ptr]),
@@ -1079,6 +1093,40 @@ class Derp:
                                            int(bool(u8)), _p(out)))
         return out
 
+    # ---- RigAnalyzer: how many cameras see each point
+    def coverage_directions(self, units, distances, want_counts=True):
+        """units [n, 3] float64, distances [nd] float64 -> (hist [nd, S + 1] int32, counts [nd, n] uint8 or None)"""
+        u = np.ascontiguousarray(units, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(distances, dtype=np.float64).reshape(-1)
+        hist = np.zeros((len(d), self.D + 1), dtype=np.int32)
+        counts = np.zeros((len(d), len(u)), dtype=np.uint8) if want_counts else None
+        self._ck(lib().derp_coverage_directions(self.h, _p(u), len(u), _p(d), len(d), _p(hist), _p(counts)))
+        return hist, counts
+
+    def coverage_equirect(self, pixels_per_degree=5, distance=1e4, timing=True):
+        """-> (counts [H, W] uint8, min_timing [H, W] float32 or None, (holes, maxMin, aveMin) or None)"""
+        ppd = int(pixels_per_degree)
+        shape = (180 * max(ppd, 0), 360 * max(ppd, 0))
+        counts = np.zeros(shape, dtype=np.uint8)
+        mt = np.zeros(shape, dtype=np.float32) if timing else None
+        stats = np.zeros(3, dtype=np.float64) if timing else None
+        self._ck(lib().derp_coverage_equirect(self.h, ppd, float(distance), _p(counts), _p(mt), _p(stats)))
+        return counts, mt, (None if stats is None else tuple(float(v) for v in stats))
+
+    def coverage_camera(self, cam, distance=1e4):
+        """-> counts [h, w] uint8 over the pixels of camera `cam` at its own resolution; 0 outside the image circle"""
+        cam = int(cam)
+        res = self.cams_dst[cam]["resolution"] if 0 <= cam < self.D else (0, 0)
+        counts = np.zeros((int(res[1]), int(res[0])), dtype=np.uint8)
+        self._ck(lib().derp_coverage_camera(self.h, cam, float(distance), _p(counts)))
+        return counts
+
+    def coverage_cross_section(self, dim=400):
+        """-> counts [dim, dim] uint8 over the plane z = 0, one unit per pixel, centred on the rig's origin"""
+        counts = np.zeros((max(int(dim), 0),) * 2, dtype=np.uint8)
+        self._ck(lib().derp_coverage_cross_section(self.h, int(dim), _p(counts)))
+        return counts
+
     # ---- AlignColors: red and blue resampled onto the green rig (DESIGN §8.8)
     def align_setup(self, red_ref, green_ref, blue_ref):
         """red_ref / green_ref / blue_ref: the cameras (dicts) of the three reference rigs, one each; builds the warp
@@ -1167,6 +1215,104 @@ def rig_center(cams, index):
             cam[k] = [float(v) for v in getattr(j, k)]
         out.append(cam)
     return out
+
+
+# ---- RigAnalyzer's rig construction and editing, on the host
+RIG_ARRANGEMENTS = ("ballcam24", "tetra", "tetratilted", "ring4", "cube", "carbon0", "carbon1", "diamond")
+
+
+def _descs(cams):
+    return (CameraDesc * len(cams))(*[camera_desc(c) for c in cams])
+
+
+def _cam_dict(template, j):
+    """the camera dict `template` with what derp_rig_* may change taken from the descriptor j"""
+    cam = dict(template)
+    for k in ("origin", "forward", "up", "right", "resolution", "focal"):
+        cam[k] = [float(v) for v in getattr(j, k)]
+    cam.pop("principal", None)
+    if j.has_principal:
+        cam["principal"] = [float(v) for v in j.principal]
+    cam["id"] = j.id.decode()
+    return cam
+
+
+def _rename(cams, one_based):
+    """--one_based_indexing: cam0, cam1, ... become cam1, cam2, ..."""
+    return [dict(c, id="cam%d" % (i + 1)) for i, c in enumerate(cams)] if one_based else cams
+
+
+def rig_fibonacci_units(count, discard_poles_deg=0.0):
+    """RigAnalyzer's sample directions -> [kept, 3] float64"""
+    out, kept = np.zeros((max(int(count), 0), 3), dtype=np.float64), C.c_int()
+    _host_ck(lib().derp_rig_fibonacci_units(int(count), float(discard_poles_deg), _p(out), C.byref(kept)))
+    return out[:kept.value].copy()
+
+
+def rig_coverage_distances(min_distance=0.5):
+    """RigAnalyzer's 20 sweep distances -> [20] float64"""
+    out = np.zeros(20, dtype=np.float64)
+    _host_ck(lib().derp_rig_coverage_distances(float(min_distance), _p(out)))
+    return out
+
+
+def rig_euler_matrix(euler_rad, xyz=True):
+    """rotationMatrixFromEulers -> [3, 3] float64"""
+    e, m = np.ascontiguousarray(euler_rad, dtype=np.float64).reshape(3), np.zeros((3, 3), dtype=np.float64)
+    _host_ck(lib().derp_rig_euler_matrix(_p(e), int(bool(xyz)), _p(m)))
+    return m
+
+
+def rig_align_z_matrix(position):
+    """--rotate_cam_z's rotation for a camera at `position` -> [3, 3] float64"""
+    p, m = np.ascontiguousarray(position, dtype=np.float64).reshape(3), np.zeros((3, 3), dtype=np.float64)
+    _host_ck(lib().derp_rig_align_z_matrix(_p(p), _p(m)))
+    return m
+
+
+def rig_from_eulers(model, eulers_deg, xyz=False, one_based=False):
+    """clones of the camera `model` (a dict) turned by each row of eulers_deg [n, 3] -> cameras cam0, cam1, ..."""
+    e = np.ascontiguousarray(eulers_deg, dtype=np.float64).reshape(-1, 3)
+    out = (CameraDesc * max(len(e), 1))()
+    _host_ck(lib().derp_rig_from_eulers(C.byref(camera_desc(model)), _p(e), len(e), int(bool(xyz)), out))
+    return _rename([_cam_dict(model, j) for j in out[:len(e)]], one_based)
+
+
+def rig_arrangement(name, model, custom=-1.0, one_based=False):
+    """one of RIG_ARRANGEMENTS built from the camera `model`; raises DerpError on an unknown name"""
+    out, n = (CameraDesc * 24)(), C.c_int()
+    _host_ck(lib().derp_rig_arrangement(name.encode(), C.byref(camera_desc(model)), float(custom), out, C.byref(n)))
+    return _rename([_cam_dict(model, j) for j in out[:n.value]], one_based)
+
+
+def rig_revolve(cams, eulers_rad):
+    """the rig repeated once per row of eulers_rad [m, 3] (radians), turned by it -> m * n cameras"""
+    e = np.ascontiguousarray(eulers_rad, dtype=np.float64).reshape(-1, 3)
+    out = (CameraDesc * max(len(e) * len(cams), 1))()
+    _host_ck(lib().derp_rig_revolve(_descs(cams), len(cams), _p(e), len(e), out))
+    return [_cam_dict(cams[i % len(cams)], j) for i, j in enumerate(out[:len(e) * len(cams)])]
+
+
+def rig_rotate(cams, matrix):
+    """every camera's position and rotation turned by the 3 x 3 `matrix`"""
+    m = np.ascontiguousarray(matrix, dtype=np.float64).reshape(3, 3)
+    out = (CameraDesc * max(len(cams), 1))()
+    _host_ck(lib().derp_rig_rotate(_descs(cams), len(cams), _p(m), out))
+    return [_cam_dict(c, j) for c, j in zip(cams, out)]
+
+
+def rig_perturb(cams, seed=1, positions=0.0, rotations=0.0, principals=0.0, focals=0.0):
+    """Camera::perturbCameras after std::srand(seed); camera 0 keeps its pose"""
+    a = _descs(cams)
+    _host_ck(lib().derp_rig_perturb(a, len(cams), int(seed), float(positions), float(rotations), float(principals), float(focals)))
+    return [_cam_dict(c, j) for c, j in zip(cams, a)]
+
+
+def rig_scale(cams, scale_rig=1.0, radius=0.0, scale_resolution=1.0):
+    """--scale_rig, --radius and --scale_resolution, in that order"""
+    a = _descs(cams)
+    _host_ck(lib().derp_rig_scale(a, len(cams), float(scale_rig), float(radius), float(scale_resolution)))
+    return [_cam_dict(c, j) for c, j in zip(cams, a)]
 
 
 def align_derive_cameras(green, red_ref, green_ref, blue_ref):

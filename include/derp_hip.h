@@ -440,6 +440,47 @@ int derp_sweep_overlap_disparities(int num_depths, uint64_t min_depth_m, uint64_
 int derp_sweep_equirect_depths(int num_depths, double depth_min, double depth_max, float* depths, int* stems);
 int derp_sweep_crop_size(int height, const int* bounds, int* new_width);
 int derp_rig_center(const derp_camera_desc* cams, int n, int index, derp_camera_desc* out_cams);
+/* ---- RigAnalyzer (source/rig/RigAnalyzer.cpp): how many cameras of the rig see each point of a point set, and the rig
+ * construction and editing that goes with it ----
+ * The cameras are the destinations of derp_create (the whole rig, in their own pixel units); each is asked with
+ * Camera::sees (Camera.h:184-190). At most 255 cameras (the counts are 8-bit); the depth path's camera cap does not apply.
+ * derp_coverage_directions: the sweep of main() (:567-577): points distances[i] * units[j] -> hist [nd][S + 1], the number
+ *   of directions seen by exactly k cameras at each distance, and counts [nd][n] (may be NULL).
+ * derp_coverage_equirect: saveEquirect (:376-438) at 360 x 180 degrees times pixels_per_degree (the reference: 5) ->
+ *   counts [H][W]; min_timing [H][W] (may be NULL): the smallest |t_i - t_j| over the pairs of cameras that see the pixel,
+ *   t = float(pix.y / resolution.y), 1 with fewer than two; stats (may be NULL) = {holes, maxMin, aveMin} summed on the
+ *   host in row-major order, aveMin being the sum, not the mean.
+ * derp_coverage_camera: saveCamera (:346-374): the pixels of camera `cam` at its own resolution, at `distance`; 0 outside
+ *   the image circle -> counts [h][w].
+ * derp_coverage_cross_section: saveCrossSection (:440-460) with kDim = dim (the reference: 400) -> counts [dim][dim].
+ * Host only, no context and no device; a refusal leaves its text in derp_last_error(NULL):
+ * derp_rig_fibonacci_units: getFibonacciUnits + discardPoles (:68-94) -> out_xyz [count][3], of which *kept are filled.
+ * derp_rig_coverage_distances: the 20 distances of :562-565.
+ * derp_rig_euler_matrix: rotationMatrixFromEulers (:96-101), radians -> row-major 3 x 3.
+ * derp_rig_align_z_matrix: --rotate_cam_z's rotation (:505-510) for a camera at `position`.
+ * derp_rig_from_eulers: makeRigFromEulers (:103-131), degrees, ids cam0, cam1, ...
+ * derp_rig_arrangement: makeNamedArrangement (:240-259, tables :157-238) -> out (room for DERP_RIG_ARRANGEMENT_MAX), *n.
+ * derp_rig_revolve: revolveRig (:133-155), radians -> out [m][n]; ids gain _<frame> when m > 1.
+ * derp_rig_rotate: position = m * position, setRotation(m * forward, m * up, m * right) (:511-516, :532-535).
+ * derp_rig_perturb: std::srand(seed) + Camera::perturbCameras (Camera.cpp:260-280), in place.
+ * derp_rig_scale: --scale_rig, --radius, --scale_resolution (:538-555), in place; 1, 0, 1 change nothing. */
+enum { DERP_RIG_COVERAGE_DISTANCES = 20, DERP_RIG_ARRANGEMENT_MAX = 24 };
+int derp_coverage_directions(derp_ctx* ctx, const double* units_xyz, int n, const double* distances, int nd, int32_t* hist,
+                             uint8_t* counts);
+int derp_coverage_equirect(derp_ctx* ctx, int pixels_per_degree, double distance, uint8_t* counts, float* min_timing,
+                           double* stats);
+int derp_coverage_camera(derp_ctx* ctx, int cam, double distance, uint8_t* counts);
+int derp_coverage_cross_section(derp_ctx* ctx, int dim, uint8_t* counts);
+int derp_rig_fibonacci_units(int count, double discard_poles_deg, double* out_xyz, int* kept);
+int derp_rig_coverage_distances(double min_distance, double* out);
+int derp_rig_euler_matrix(const double* euler_rad, int xyz, double* m9);
+int derp_rig_align_z_matrix(const double* position, double* m9);
+int derp_rig_from_eulers(const derp_camera_desc* model, const double* eulers_deg, int n, int xyz, derp_camera_desc* out);
+int derp_rig_arrangement(const char* name, const derp_camera_desc* model, double custom, derp_camera_desc* out, int* n);
+int derp_rig_revolve(const derp_camera_desc* cams, int n, const double* eulers, int m, derp_camera_desc* out);
+int derp_rig_rotate(const derp_camera_desc* cams, int n, const double* m9, derp_camera_desc* out);
+int derp_rig_perturb(derp_camera_desc* cams, int n, int seed, double pos, double rot, double principal, double focal);
+int derp_rig_scale(derp_camera_desc* cams, int n, double scale_rig, double radius, double scale_resolution);
 /* ---- AlignColors (source/calibration/AlignColors.cpp): the red and blue planes of every camera resampled through
  * per-channel lens models onto the calibrated (green) rig, ahead of the pyramid ----
  * The cameras are the destinations of derp_create: the calibrated rig after --cameras, not normalised. Images are
