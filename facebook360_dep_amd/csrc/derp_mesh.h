@@ -61,6 +61,27 @@ __global__ void __launch_bounds__(kMeshBlock)
   valid[i] = ok;
 }
 
+// ---- getVertexesEquirect (MeshUtil.h:298-314): depth = fmin(maxDepth, 1.0f / disparity) in float, times the unit
+// direction of the pixel's centre in fp64. theta depends on the column and phi on the row alone: tabs holds cos(theta) [W],
+// sin(theta) [W], sin(phi) [H], cos(phi) [H], computed on the host as the reference's expressions round them. norm = the
+// vertex's distance from the rig centre as Eigen's row norm sums it, which is getTriangleMask's key in rig coordinates.
+__global__ void __launch_bounds__(kMeshBlock)
+    k_mesh_vertices_equirect(const float* __restrict__ disparity, int W, int H, float maxDepth, const double* __restrict__ tabs,
+                             double* __restrict__ V, double* __restrict__ norm) {
+  const size_t i = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
+  if (i >= (size_t)W * H) {
+    return;
+  }
+  const int x = (int)(i % W), y = (int)(i / W);
+  const double depth = (double)fminf(maxDepth, 1.0f / disparity[i]);
+  const double sinPhi = tabs[2 * (size_t)W + y], cosPhi = tabs[2 * (size_t)W + H + y];
+  const double px = depth * (sinPhi * tabs[x]), py = depth * cosPhi, pz = depth * (sinPhi * tabs[(size_t)W + x]);
+  V[3 * i] = px;
+  V[3 * i + 1] = py;
+  V[3 * i + 2] = pz;
+  norm[i] = sqrt((px * px + py * py) + pz * pz);
+}
+
 // ---- getTriangleMask for camera meshes (isRigCoordinates = false: the key is the vertex's z) -----------------------
 // std::sort of four (z, corner) tuples is libstdc++'s insertion sort with the tuples' lexicographic operator<; written
 // out so that a NaN key (a comparator that is no strict weak order) lands where it lands there.
@@ -131,9 +152,10 @@ __host__ __device__ __forceinline__ unsigned mesh_triangle_mask(double tl, doubl
 
 // Every pixel is the base (top-left corner) of one quad, except in the last column and row. qmask = the quad's triangle
 // mask (low nibble) and the triangles of it whose three vertices pass the vertex mask (high nibble). Triangle t of a
-// quad (addTriangle) has every corner but t ^ 3.
+// quad (addTriangle) has every corner but t ^ 3. key[keyStride * pixel] = getTriangleMask's depth of the pixel's vertex:
+// its z in a camera mesh, its norm in rig coordinates. valid == nullptr: no vertex mask.
 __global__ void __launch_bounds__(kMeshBlock)
-    k_mesh_quads(const double* __restrict__ vert, const uint8_t* __restrict__ valid, int W, int H, float tearRatio,
+    k_mesh_quads(const double* __restrict__ key, int keyStride, const uint8_t* __restrict__ valid, int W, int H, float tearRatio,
                  uint8_t* __restrict__ qmask, uint32_t* __restrict__ blockFaces, unsigned long long* __restrict__ unmasked) {
   __shared__ uint32_t waveTotal[kMeshBlock / 64];
   __shared__ uint32_t rawTotal[kMeshBlock / 64];
@@ -144,10 +166,13 @@ __global__ void __launch_bounds__(kMeshBlock)
     const int x = (int)(i % W), y = (int)(i / W);
     if (x < W - 1 && y < H - 1) {
       const size_t c[4] = {i, i + 1, i + (size_t)W, i + (size_t)W + 1};
-      tm = mesh_triangle_mask(vert[3 * c[0] + 2], vert[3 * c[1] + 2], vert[3 * c[2] + 2], vert[3 * c[3] + 2], tearRatio);
-      unsigned ok = 0;
-      for (int k = 0; k < 4; ++k) {
-        ok |= (valid[c[k]] ? 1u : 0u) << k;
+      tm = mesh_triangle_mask(key[keyStride * c[0]], key[keyStride * c[1]], key[keyStride * c[2]], key[keyStride * c[3]],
+                              tearRatio);
+      unsigned ok = valid ? 0u : 0xfu;
+      if (valid) {
+        for (int k = 0; k < 4; ++k) {
+          ok |= (valid[c[k]] ? 1u : 0u) << k;
+        }
       }
       for (int t = 0; t < 4; ++t) {
         const unsigned need = 0xfu & ~(1u << (t ^ 3));
@@ -235,8 +260,8 @@ __global__ void __launch_bounds__(kMeshBlock)
   }
 }
 
-// kept faces in row-major quad order, triangles 0..3 ascending, addTriangle's vertex orders, re-indexed; qoff = the
-// index of every quad's first kept face
+// kept faces in row-major quad order, triangles 0..3 ascending, addTriangle's vertex orders, re-indexed (vmap ==
+// nullptr: every vertex keeps its pixel's index); qoff = the index of every quad's first kept face
 __global__ void __launch_bounds__(kMeshBlock)
     k_mesh_face_scatter(const uint8_t* __restrict__ qmask, int W, int H, const unsigned long long* __restrict__ blockOffset,
                         const uint32_t* __restrict__ vmap, uint32_t* __restrict__ qoff, int32_t* __restrict__ outF) {
@@ -259,11 +284,28 @@ __global__ void __launch_bounds__(kMeshBlock)
   for (int t = 0; t < 4; ++t) {
     if (km >> t & 1) {
       for (int k = 0; k < 3; ++k) {
-        outF[3 * f + k] = (int32_t)vmap[tri[t][k]];
+        outF[3 * f + k] = (int32_t)(vmap ? vmap[tri[t][k]] : (uint32_t)tri[t][k]);
       }
       ++f;
     }
   }
+}
+
+// getFaces' wrapHorizontally (MeshUtil.h:285-293): after the last grid face, two faces per row that link column W - 1
+// back to column 0, in row order, with no tear test
+__global__ void __launch_bounds__(kMeshBlock) k_mesh_seam_faces(int W, int H, size_t firstSeamFace, int32_t* __restrict__ outF) {
+  const int y = blockIdx.x * kMeshBlock + threadIdx.x;
+  if (y >= H - 1) {
+    return;
+  }
+  const int32_t base = y * W;
+  int32_t* f = outF + 3 * (firstSeamFace + 2 * (size_t)y);
+  f[0] = base + W;
+  f[1] = base;
+  f[2] = base + W - 1;
+  f[3] = base + W - 1;
+  f[4] = base + 2 * W - 1;
+  f[5] = base + W;
 }
 
 // ---- MeshSimplifier::computeInitialQuadrics on the compacted mesh ---------------------------------------------------
@@ -288,16 +330,18 @@ __global__ void __launch_bounds__(kMeshBlock)
 
 // "Accumulating quadrics...": vertex.q += face.q over the faces in ascending index. A vertex's faces lie in the four
 // quads around it, whose faces are numbered in the order (x-1, y-1), (x, y-1), (x-1, y), (x, y), triangles ascending:
-// a gather in that order is the sequential sum, with no atomics.
+// a gather in that order is the sequential sum, with no atomics. vorig == nullptr: the mesh is the whole grid. seam:
+// the mesh has k_mesh_seam_faces' faces from index firstSeamFace on; those of a vertex of column 0 or W - 1 follow all
+// its grid faces, by ascending row: (y - 1: both, y: the first) in column 0, (y - 1: the second, y: both) in column W - 1.
 __global__ void __launch_bounds__(kMeshBlock)
     k_mesh_vertex_quadrics(const uint8_t* __restrict__ qmask, const uint32_t* __restrict__ qoff,
                            const uint32_t* __restrict__ vorig, int W, int H, size_t nv, const double* __restrict__ planes,
-                           double* __restrict__ vq) {
+                           int seam, size_t firstSeamFace, double* __restrict__ vq) {
   const size_t v = (size_t)blockIdx.x * kMeshBlock + threadIdx.x;
   if (v >= nv) {
     return;
   }
-  const uint32_t i = vorig[v];
+  const uint32_t i = vorig ? vorig[v] : (uint32_t)v;
   const int x = (int)(i % (uint32_t)W), y = (int)(i / (uint32_t)W);
   double Q[derp_mesh::kQuadric];
   for (int k = 0; k < derp_mesh::kQuadric; ++k) {
@@ -321,6 +365,21 @@ __global__ void __launch_bounds__(kMeshBlock)
           derp_mesh::add_plane_quadric(Q, q4);
         }
         ++f;
+      }
+    }
+  }
+  if (seam && (x == 0 || x == W - 1)) {
+    // the seam faces of rows y - 1 and y as a run of four; bit k set = face firstSeamFace + 2 (y - 1) + k holds the vertex
+    const unsigned has = x == 0 ? 0x7u : 0xeu;
+    for (int k = 0; k < 4; ++k) {
+      const int row = y - 1 + (k >> 1);
+      if ((has >> k & 1) && row >= 0 && row < H - 1) {
+        const size_t f = firstSeamFace + 2 * (size_t)row + (k & 1);
+        double q4[4];
+        for (int j = 0; j < 4; ++j) {
+          q4[j] = planes[4 * f + j];
+        }
+        derp_mesh::add_plane_quadric(Q, q4);
       }
     }
   }

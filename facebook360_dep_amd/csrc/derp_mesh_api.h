@@ -1,17 +1,20 @@
-// ConvertToBinary's camera meshes, host side: build, quadric set-up, the drivers of the host simplifier
-// (derp_simplify.cpp) and of the pass-parallel one. Kernels: derp_mesh.h. Included by derp_capi.hip after the depth core.
+// ConvertToBinary's camera meshes and CreateObjFromDisparityEquirect's wrapped scene mesh, host side: build, quadric
+// set-up, the drivers of the host simplifier (derp_simplify.cpp) and of the pass-parallel one. Kernels: derp_mesh.h.
+// Included by derp_capi.hip after the depth core.
 #pragma once
 
 namespace {
 
-// derp_mesh_*: one camera's mesh (derp_mesh.h). The grid-sized buffers stay for the next camera; the compacted mesh
-// (V, F) and what the set-up gathers through (qmask, qoff, vorig) describe the mesh built last.
+// derp_mesh_*: one camera's mesh, or one equirect's (derp_mesh.h). The grid-sized buffers stay for the next mesh; the
+// compacted mesh (V, F) and what the set-up gathers through (qmask, qoff, vorig) describe the mesh built last. An
+// equirect mesh keeps the whole grid (no vorig) and ends in its seam faces, from index nfGrid on.
 struct MeshState {
   DevBuf disparity, mask, tabs, vert, valid, qmask, used, blockFaces, blockVerts, offF, offV, totals, vmap, vorig, qoff, V, F;
+  DevBuf norm;
   DevBuf planes, costs, vq;
   int W = 0, H = 0;
-  size_t nv = 0, nf = 0, nfUnmasked = 0;
-  bool built = false;
+  size_t nv = 0, nf = 0, nfUnmasked = 0, nfGrid = 0;
+  bool built = false, equirect = false;
   // derp_mesh_simplify's / derp_mesh_simplify_parallel's result (host): what the downloads return once one has run
   bool simplified = false;
   std::vector<double> sV;
@@ -35,7 +38,7 @@ int need_mesh(derp_ctx* c) {
     return 1;
   }
   if (!c->mesh || !c->mesh->built) {
-    return fail(c, "derp_mesh_build has not been called");
+    return fail(c, "derp_mesh_build has not been called");  // (nor derp_mesh_build_equirect)
   }
   return 0;
 }
@@ -51,8 +54,8 @@ int mesh_setup_dev(derp_ctx* c, int equi_error) {
   hipLaunchKernelGGL(k_mesh_face_planes, dim3(blocks_of(m.nf, kMeshBlock)), dim3(kMeshBlock), 0, c->stream, m.V.as<double>(),
                      m.F.as<int32_t>(), m.nf, m.planes.as<double>());
   hipLaunchKernelGGL(k_mesh_vertex_quadrics, dim3(blocks_of(m.nv, kMeshBlock)), dim3(kMeshBlock), 0, c->stream,
-                     m.qmask.as<uint8_t>(), m.qoff.as<uint32_t>(), m.vorig.as<uint32_t>(), m.W, m.H, m.nv, m.planes.as<double>(),
-                     m.vq.as<double>());
+                     m.qmask.as<uint8_t>(), m.qoff.as<uint32_t>(), m.equirect ? (const uint32_t*)nullptr : m.vorig.as<uint32_t>(),
+                     m.W, m.H, m.nv, m.planes.as<double>(), m.equirect ? 1 : 0, m.nfGrid, m.vq.as<double>());
   hipLaunchKernelGGL(k_mesh_edge_costs, dim3(blocks_of(m.nf * 3, kMeshBlock)), dim3(kMeshBlock), 0, c->stream, m.V.as<double>(),
                      m.F.as<int32_t>(), m.nf, m.vq.as<double>(), equi_error, m.costs.as<double>());
   KCHECK(c);
@@ -99,7 +102,7 @@ int derp_mesh_build(derp_ctx* c, int cam, const float* disparity, int w, int h, 
     c->mesh.reset(new MeshState);
   }
   MeshState& m = *c->mesh;
-  m.built = m.simplified = false;
+  m.built = m.simplified = m.equirect = false;
   m.W = W;
   m.H = H;
   std::vector<int> tabs(2 * (size_t)W + 2 * (size_t)H);
@@ -134,8 +137,8 @@ int derp_mesh_build(derp_ctx* c, int cam, const float* disparity, int w, int h, 
   hipLaunchKernelGGL(k_mesh_vertices, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.disparity.as<float>(), w, dt, dt + W, W, H,
                      resx, resy, fx, mask ? m.mask.as<uint8_t>() : (const uint8_t*)nullptr, mask_w, dt + W + H,
                      dt + 2 * W + H, m.vert.as<double>(), m.valid.as<uint8_t>());
-  hipLaunchKernelGGL(k_mesh_quads, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.vert.as<double>(), m.valid.as<uint8_t>(), W, H,
-                     tear_ratio, m.qmask.as<uint8_t>(), m.blockFaces.as<uint32_t>(), totals + 2);
+  hipLaunchKernelGGL(k_mesh_quads, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.vert.as<double>() + 2, 3, m.valid.as<uint8_t>(),
+                     W, H, tear_ratio, m.qmask.as<uint8_t>(), m.blockFaces.as<uint32_t>(), totals + 2);
   hipLaunchKernelGGL(k_mesh_vertex_used, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.qmask.as<uint8_t>(), W, H,
                      m.used.as<uint8_t>(), m.blockVerts.as<uint32_t>());
   hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, m.blockFaces.as<uint32_t>(), nb,
@@ -148,6 +151,7 @@ int derp_mesh_build(derp_ctx* c, int cam, const float* disparity, int w, int h, 
   m.nf = (size_t)t[0];
   m.nv = (size_t)t[1];
   m.nfUnmasked = (size_t)t[2];
+  m.nfGrid = m.nf;
   if (m.nv > n || m.nf > 2 * n) {
     return fail(c, "derp_mesh_build: inconsistent counts (%zu vertices, %zu faces for %zu pixels)", m.nv, m.nf, n);
   }
@@ -160,6 +164,89 @@ int derp_mesh_build(derp_ctx* c, int cam, const float* disparity, int w, int h, 
                      m.offF.as<unsigned long long>(), m.vmap.as<uint32_t>(), m.qoff.as<uint32_t>(), m.F.as<int32_t>());
   KCHECK(c);
   m.built = true;
+  return 0;
+}
+
+// getVertexesEquirect + getFaces(wrapHorizontally = true, isRigCoordinates = true) (MeshUtil.h:264-314). Nothing is
+// compacted: the vertices are the grid, and the set-up reads them as such.
+int derp_mesh_build_equirect(derp_ctx* c, const float* disparity, int w, int h, float max_depth, float tear_ratio) {
+  if (!c || !disparity) {
+    return fail(c, "derp_mesh_build_equirect: null pointer");
+  }
+  if (w < 2 || h < 2) {
+    return fail(c, "derp_mesh_build_equirect: a %d x %d equirect (the seam needs 2 columns, a face 2 rows)", w, h);
+  }
+  if ((size_t)w * h >= kMaxPixels) {
+    return fail(c, "derp_mesh_build_equirect: %d x %d pixels are more than an index holds", w, h);
+  }
+  if (tear_ratio != tear_ratio) {
+    return fail(c, "derp_mesh_build_equirect: tear_ratio is NaN");
+  }
+  if (max_depth != max_depth) {
+    return fail(c, "derp_mesh_build_equirect: max_depth is NaN");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the mesh built before this one may still be read
+  if (!c->mesh) {
+    c->mesh.reset(new MeshState);
+  }
+  MeshState& m = *c->mesh;
+  m.built = m.simplified = m.equirect = false;
+  m.W = w;
+  m.H = h;
+  // `const float theta = u * 2.0f * M_PI`, `phi = v * M_PI` with u = float(x + 0.5) / float(width): the products with
+  // M_PI are doubles, narrowed; sin / cos of them are the C library's double functions
+  std::vector<double> tabs(2 * (size_t)w + 2 * (size_t)h);
+  for (int x = 0; x < w; ++x) {
+    const float u = float(x + 0.5) / float(w);
+    const float theta = (float)(u * 2.0f * M_PI);
+    tabs[x] = std::cos((double)theta);
+    tabs[(size_t)w + x] = std::sin((double)theta);
+  }
+  for (int y = 0; y < h; ++y) {
+    const float v = float(y + 0.5) / float(h);
+    const float phi = (float)(v * M_PI);
+    tabs[2 * (size_t)w + y] = std::sin((double)phi);
+    tabs[2 * (size_t)w + h + y] = std::cos((double)phi);
+  }
+  const size_t n = (size_t)w * h;
+  const int nb = (int)blocks_of(n, kMeshBlock);
+  TRY(upload_sync(c, m.disparity, disparity, n * 4));
+  TRY(upload_sync(c, m.tabs, tabs.data(), tabs.size() * 8));
+  ALLOC(c, m.V, n * 24);
+  ALLOC(c, m.norm, n * 8);
+  ALLOC(c, m.qmask, n);
+  ALLOC(c, m.used, n);      // (derp_mesh_simplify_parallel's createFinalMesh works in these two)
+  ALLOC(c, m.vmap, n * 4);
+  ALLOC(c, m.qoff, n * 4);
+  ALLOC(c, m.blockFaces, (size_t)nb * 4);
+  ALLOC(c, m.offF, (size_t)nb * 8);
+  ALLOC(c, m.totals, 24);
+  unsigned long long* totals = m.totals.as<unsigned long long>();  // grid faces, -, the same again
+  HIPCHK(c, hipMemsetAsync(totals, 0, 24, c->stream));
+  hipLaunchKernelGGL(k_mesh_vertices_equirect, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.disparity.as<float>(), w, h, max_depth,
+                     m.tabs.as<double>(), m.V.as<double>(), m.norm.as<double>());
+  hipLaunchKernelGGL(k_mesh_quads, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.norm.as<double>(), 1, (const uint8_t*)nullptr, w, h,
+                     tear_ratio, m.qmask.as<uint8_t>(), m.blockFaces.as<uint32_t>(), totals + 2);
+  hipLaunchKernelGGL(k_scan_block_counts, dim3(1), dim3(1024), 0, c->stream, m.blockFaces.as<uint32_t>(), nb,
+                     m.offF.as<unsigned long long>(), totals);
+  KCHECK(c);
+  unsigned long long t[3] = {0, 0, 0};
+  TRY(download_sync(c, t, totals, 24));
+  const size_t seamFaces = 2 * (size_t)(h - 1);
+  if (t[0] != t[2] || t[0] > 2 * (size_t)(w - 1) * (size_t)(h - 1)) {
+    return fail(c, "derp_mesh_build_equirect: inconsistent counts (%llu and %llu faces for %zu pixels)", t[0], t[2], n);
+  }
+  m.nfGrid = (size_t)t[0];
+  m.nf = m.nfUnmasked = m.nfGrid + seamFaces;
+  m.nv = n;
+  ALLOC(c, m.F, m.nf * 12);
+  hipLaunchKernelGGL(k_mesh_face_scatter, dim3(nb), dim3(kMeshBlock), 0, c->stream, m.qmask.as<uint8_t>(), w, h,
+                     m.offF.as<unsigned long long>(), (const uint32_t*)nullptr, m.qoff.as<uint32_t>(), m.F.as<int32_t>());
+  hipLaunchKernelGGL(k_mesh_seam_faces, dim3(blocks_of((size_t)h - 1, kMeshBlock)), dim3(kMeshBlock), 0, c->stream, w, h, m.nfGrid,
+                     m.F.as<int32_t>());
+  KCHECK(c);
+  m.built = m.equirect = true;
   return 0;
 }
 

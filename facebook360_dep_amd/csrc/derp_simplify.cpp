@@ -364,3 +364,18 @@ extern "C" int derp_mesh_simplify_host(const double* vertices, size_t nv, const 
   }
   return 0;
 }
+
+// addTextureCoordinatesEquirect (MeshUtil.h:407-419): "texture goes +x, +z, -x, -z, +x from left to right (0 to 1) and
+// -y to +y from top to bottom (0 to 1)"
+extern "C" int derp_mesh_texcoords_equirect(const double* vertices, size_t nv, double* st) {
+  if ((!vertices || !st) && nv) {
+    return 1;
+  }
+  for (size_t v = 0; v < nv; ++v) {
+    const double x = vertices[3 * v], y = vertices[3 * v + 1], z = vertices[3 * v + 2];
+    const double xzNorm = std::sqrt(x * x + z * z);
+    st[2 * v] = std::atan2(-z, -x) * 0.5 / M_PI + 0.5;
+    st[2 * v + 1] = -std::atan2(-y, xzNorm) / M_PI + 0.5;
+  }
+  return 0;
+}

@@ -199,6 +199,7 @@ PROTOTYPES = {
     "derp_points_download": (_int, [_ptr, _int, _ptr]),
     "derp_project_equirect_mask": (_int, [_ptr, _int, _ptr, _int, _int, _int, _int, _f64, _ptr]),
     "derp_mesh_build": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _f64, _ptr, _int, _int, _f32]),
+    "derp_mesh_build_equirect": (_int, [_ptr, _ptr, _int, _int, _f32, _f32]),
     "derp_mesh_counts": (_int, [_ptr, _ptr, _ptr, _ptr]),
     "derp_mesh_setup": (_int, [_ptr, _int, _ptr, _ptr, _ptr]),
     "derp_mesh_simplify": (_int, [_ptr, _int, _f32, _int, _int, _int, _ptr]),
@@ -245,6 +246,7 @@ PROTOTYPES = {
     "derp_mesh_setup_host": (_int, [_ptr, _size, _ptr, _size, _int, _ptr, _ptr, _ptr]),
     "derp_mesh_simplify_host": (_int, [_ptr, _size, _ptr, _size, _ptr, _ptr, _ptr, _int, _f32, _int, _int, _ptr, _ptr, _ptr,
                                       _ptr, _ptr]),
+    "derp_mesh_texcoords_equirect": (_int, [_ptr, _size, _ptr]),
     "derp_fov_mask": (_int, [_ptr, _int, _int, _int, _ptr]),
     "derp_upsample_disparity": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _ptr, _ptr, _int, _int, _int, _ptr]),
     "derp_joint_bilateral_u16": (_int, [_ptr, _ptr, _ptr, _ptr, _int, _int, _int, _f32, _f32, _f32, _f32, _ptr]),
@@ -885,6 +887,15 @@ class Derp:
         self._ck(lib().derp_mesh_build(self.h, cam, _p(disparity), w, h, res, depth_scale, _p(mask), mw, mh, tear_ratio))
         return self.mesh_counts()
 
+    def mesh_build_equirect(self, disparity, max_depth=700.0, tear_ratio=0.95):
+        """getVertexesEquirect + getFaces(wrap, rig coordinates) (MeshUtil.h:264-314) of a disparity equirect f32
+        [h, w]: the whole grid as vertices, the seam faces last. The context's cameras are not read; the other mesh_*
+        methods then work on this mesh, with equi_error=False. -> (vertices, faces, faces again)."""
+        disparity = np.ascontiguousarray(disparity, dtype=np.float32)
+        h, w = disparity.shape
+        self._ck(lib().derp_mesh_build_equirect(self.h, _p(disparity), w, h, max_depth, tear_ratio))
+        return self.mesh_counts()
+
     def mesh_counts(self):
         nv, nf, raw = C.c_size_t(), C.c_size_t(), C.c_size_t()
         self._ck(lib().derp_mesh_counts(self.h, C.byref(nv), C.byref(nf), C.byref(raw)))
@@ -1358,6 +1369,15 @@ def mesh_simplify_host(vertices, faces, num_faces_out, strictness=0.2, remove_bo
                                      _p(ov), _p(of), C.byref(nv), C.byref(nf), stats):
         raise DerpError("derp_mesh_simplify_host: bad arguments")
     return ov[:nv.value].copy(), of[:nf.value].copy(), (stats[0], stats[1])
+
+
+def mesh_texcoords_equirect(vertices):
+    """addTextureCoordinatesEquirect (MeshUtil.h:407-419) on the host (no device): f64 [nv, 3] -> st f64 [nv, 2]"""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    st = np.zeros((len(v), 2))
+    if lib().derp_mesh_texcoords_equirect(_p(v), len(v), _p(st)):
+        raise DerpError("derp_mesh_texcoords_equirect: bad arguments")
+    return st
 
 
 def host_nth_element_pairs(pairs, nth):

@@ -339,7 +339,16 @@ int derp_project_equirect_mask(derp_ctx* ctx, int cam, const uint8_t* eqr, int e
  * derp_mesh_parallel_pass: what pass `pass` (0 .. passes - 1) of the last derp_mesh_simplify_parallel saw.
  * derp_mesh_download_f64 / derp_mesh_download: MeshSimplifier::getVertexes / getFaces, or the built mesh when it was
  *   not simplified; the second as mesh_util::writeDepth lays the files out (MeshUtil.h:72-89): float32 x y z rows and
- *   uint32 index triples, with z < 0 raised to FLT_MIN first when clamp_negative_z (ConvertToBinary.cpp:211-217). */
+ *   uint32 index triples, with z < 0 raised to FLT_MIN first when clamp_negative_z (ConvertToBinary.cpp:211-217).
+ * derp_mesh_build_equirect: CreateObjFromDisparityEquirect's mesh (source/conversion/CreateObjFromDisparityEquirect.cpp)
+ *   of a disparity equirect [h][w], on the device: mesh_util::getVertexesEquirect and mesh_util::getFaces(wrap = true,
+ *   isRigCoordinates = true, tear_ratio) (MeshUtil.h:264-314). Vertex y * w + x is fmin(max_depth, 1.0f / disparity)
+ *   (float: a disparity of 0 or NaN gives max_depth, a negative one a negative depth) times the unit direction of the
+ *   pixel's centre, in rig coordinates; getTriangleMask reads the vertices' norms; after the grid's faces come two faces
+ *   per row that link column w - 1 to column 0, with no tear test. All w * h vertices stay, used or not, so
+ *   faces_unmasked == faces. The cameras of the context are not read. It leaves the context as derp_mesh_build does:
+ *   derp_mesh_counts / _setup / _simplify / _simplify_parallel / _parallel_pass / _download* work on the mesh, with
+ *   equi_error = 0. Refused: null pointers, w < 2 or h < 2, w * h >= 2^31, a tear_ratio or max_depth that is NaN. */
 enum {
   DERP_MESH_EXIT_BUDGET = 0,
   DERP_MESH_EXIT_INFINITE_THRESHOLD = 1,
@@ -356,6 +365,7 @@ typedef struct derp_mesh_pass {
 } derp_mesh_pass;
 int derp_mesh_build(derp_ctx* ctx, int cam, const float* disparity, int w, int h, const double* resolution,
                     double depth_scale, const uint8_t* mask, int mask_w, int mask_h, float tear_ratio);
+int derp_mesh_build_equirect(derp_ctx* ctx, const float* disparity, int w, int h, float max_depth, float tear_ratio);
 int derp_mesh_counts(derp_ctx* ctx, size_t* vertices, size_t* faces, size_t* faces_unmasked);
 int derp_mesh_setup(derp_ctx* ctx, int equi_error, double* face_planes, double* edge_costs, double* vertex_quadrics);
 int derp_mesh_simplify(derp_ctx* ctx, int num_faces_out, float strictness, int remove_boundary_edges, int equi_error,
@@ -514,13 +524,16 @@ int derp_align_frame(derp_ctx* ctx, const uint16_t* const* bgr, const int* img_w
  *   identifyBoundaries, getThreshold, haveNormalsFlipped, commonFaces, updateCosts). The set-up arrays come from
  *   derp_mesh_setup / derp_mesh_setup_host, or all three NULL: computed here. out_vertices / out_faces have room for
  *   the input's counts. One departure: a pass that deleted nothing under a zero or NaN threshold repeats for ever in
- *   the reference; here the loop ends (DERP_MESH_EXIT_STUCK). */
+ *   the reference; here the loop ends (DERP_MESH_EXIT_STUCK).
+ * derp_mesh_texcoords_equirect: mesh_util::addTextureCoordinatesEquirect (MeshUtil.h:407-419): vertices f64 [nv][3] in
+ *   rig coordinates -> st f64 [nv][2], s = atan2(-z, -x) * 0.5 / pi + 0.5, t = -atan2(-y, |(x, z)|) / pi + 0.5. */
 int derp_mesh_setup_host(const double* vertices, size_t nv, const int32_t* faces, size_t nf, int equi_error,
                          double* face_planes, double* edge_costs, double* vertex_quadrics);
 int derp_mesh_simplify_host(const double* vertices, size_t nv, const int32_t* faces, size_t nf, const double* face_planes,
                             const double* edge_costs, const double* vertex_quadrics, int num_faces_out, float strictness,
                             int remove_boundary_edges, int equi_error, double* out_vertices, int32_t* out_faces,
                             size_t* out_nv, size_t* out_nf, int* stats);
+int derp_mesh_texcoords_equirect(const double* vertices, size_t nv, double* st);
 /* generateFovMasks for one destination camera at an arbitrary size (DerpUtil.cpp:259-276) */
 int derp_fov_mask(derp_ctx* ctx, int dst, int w, int h, uint8_t* out);
 /* upsampleDisparities for one camera (UpsampleDisparityLib.cpp:98-182). fg_mask / fg_mask_up /
