@@ -444,7 +444,8 @@ int build_warp(derp_ctx* c, int dst0, int nd) {
   hipLaunchKernelGGL(k_pixel_rays, grid2d(V.W, V.H, nd, kBlk2d), kBlk2d, 0, c->stream, V, c->rayDir.as<double>(),
                      c->behind.as<unsigned>());
   KCHECK(c);
-  c->w.colorTablesCleanLevel = -1;  // new warps (another level, batch or rig state): the colour tables must be rewritten in full
+  // new warps (another level, batch or rig state): every work set's colour tables, the lanes' too, must be rewritten in full
+  ++c->warpGeneration;
   // ... and the inverse warps reprojectColors reads (projWarpInv, PyramidLevel.h:46-51) — those that are not a
   // projWarp table of this batch already (all of them are when every source is a destination of the batch)
   if (batch_needs_inverse_warps(c, dst0, nd)) {
@@ -462,14 +463,18 @@ int build_color_tables(derp_ctx* c, int dst0, int nd) {
   const dim3 grid((V.W + kRbTile - 1) / kRbTile, (V.H + kRbTile - 1) / kRbTile, nd * (c->S - 1));
   ALLOC(c, c->w.tileSeen, (size_t)grid.x * grid.y * grid.z);
   // a frame that finds the tables of this level as an earlier frame left them (same warps: a sequence running the
-  // level frame after frame) skips the tiles no source pixel maps into — they still hold their zeros
-  const int skipBlank = c->w.colorTablesCleanLevel == L && nd == c->D && !c->noBlankSkip;
+  // level frame after frame) skips the tiles no source pixel maps into — they still hold their zeros. The level index
+  // alone does not say so: this work set may have met the index last under other warps or another geometry (a lane keeps
+  // its state from sequence to sequence), with its tables and flags laid out for those.
+  const int skipBlank = c->w.colorTablesCleanLevel == L && c->w.colorTablesWarpGeneration == c->warpGeneration &&
+      nd == c->D && !c->noBlankSkip;
   const auto kernel = c->reprojectSerial ? k_reproject_bias : k_reproject_bias_front;  // the same tables either way
   hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, V, c->projWarpInv.as<float2>(),
                      c->w.projColor.as<ushort4>(), c->w.projBias.as<ushort4>(), c->w.projColorT.as<ushort4>(),
                      c->w.tileSeen.as<uint8_t>(), skipBlank);
   KCHECK(c);
   c->w.colorTablesCleanLevel = nd == c->D ? L : -1;
+  c->w.colorTablesWarpGeneration = c->warpGeneration;
   return 0;
 }
 
@@ -1260,12 +1265,19 @@ int derp_set_pyramid(derp_ctx* c, int num_levels, const int* widths, const int* 
       return fail(c, "level %d is too large (%dx%d, a side may be 4194303 at most)", l, widths[l], heights[l]);
     }
   }
+  // a sequence sized its halo, filter and mask buffers for the geometry it was made under and indexes the frame slots
+  // this call drops: with one open, nothing changes
+  if (!c->openSeqs.empty()) {
+    return fail(c, "derp_set_pyramid: %s is still open on this context (%d open; derp_seq_destroy first)",
+                c->openSeqs.back().second.c_str(), (int)c->openSeqs.size());
+  }
   HIPCHK(c, hipSetDevice(c->device));
   c->numLevels = num_levels;
   c->widthFull = width_full;
   c->heightFull = height_full;
   c->LW.assign(widths, widths + num_levels);
   c->LH.assign(heights, heights + num_levels);
+  ++c->warpGeneration;  // no work set's colour tables or tile flags, on the context or on a lane, fit this geometry
   // a new geometry drops every frame slot (their buffers have the old sizes) and starts again with slot 0
   c->frames.clear();
   c->frames.resize(1);

@@ -68,7 +68,10 @@ struct WorkSet {
   DevBuf projColorT;  // projColor again in 4x4-texel tiles: the random-proposal kernel's copy (DERP_RANDOM_TILED)
   DevBuf bruteCost, bruteConf, lanczosTmp, staging, stagingB;
   bool mismatchMaskHeld = false;   // mismatchMask was cleared for the current level (the mismatch stage runs at it)
-  int colorTablesCleanLevel = -1;  // level whose colour / bias tables were written in full since its warps were built
+  // level whose colour / bias tables were written in full, and the warps they were written for (derp_ctx::warpGeneration
+  // at that time): blank tiles may be skipped only while both still hold
+  int colorTablesCleanLevel = -1;
+  uint64_t colorTablesWarpGeneration = 0;
 };
 
 // HBM-resident pyramid of one frame, per level: colour, fg masks, background disparity, result
@@ -117,6 +120,9 @@ struct derp_ctx {
   FramePyramid& frame() {
     return frames[curSlot];
   }
+  // the sequences made on this context and not destroyed yet (derp_seq_create / derp_seq_destroy), each with the words an
+  // error message names it by: their buffers have this geometry's sizes, so derp_set_pyramid refuses while one is open
+  std::vector<std::pair<const derp_seq*, std::string>> openSeqs;
   DevBuf fullFrame;  // the pyramid builder's full-size input
   DevBuf devMask;    // derp_dev_mask result (not a working buffer)
 
@@ -128,6 +134,9 @@ struct derp_ctx {
   DevBuf projWarp, projWarpInv;
   DevBuf rayDir, behind;  // per destination pixel: ray direction [3][D][n] f64, sources facing away [D][n] (k_pixel_rays)
   int warpCachedLevel = -1;
+  // counts every rebuild of the shared warps and every new geometry (build_warp, derp_set_pyramid): what a work set, the
+  // context's own or a lane's, wrote for an earlier value was written for other warps
+  uint64_t warpGeneration = 1;
   DevBuf fovMask;  // the destinations' FOV masks of level fovCachedLevel [D][n]: rig + level size only, shared by the lanes
   int fovCachedLevel = -1;
   bool randomRanThisLevel = false;  // cost / confidence hold random-proposal results for this level

@@ -478,6 +478,12 @@ int derp_seq_create(derp_seq** out, derp_ctx* c, int first, int last, int rank, 
   q->last = last;
   q->rank = rank;
   q->world = world;
+  {
+    // open from here on (derp_set_pyramid refuses); derp_seq_destroy, the early returns' too, takes it off the list
+    char name[96];
+    snprintf(name, sizeof name, "a derp_seq (frames %d..%d, rank %d of %d)", first, last, rank, world);
+    c->openSeqs.emplace_back(q, name);
+  }
   if (opt) {
     q->opt = *opt;
   } else {
@@ -610,6 +616,8 @@ void derp_seq_destroy(derp_seq* q) {
   if (q->c) {
     (void)hipSetDevice(q->c->device);
     (void)hipStreamSynchronize(q->c->stream);
+    auto& open = q->c->openSeqs;
+    open.erase(std::remove_if(open.begin(), open.end(), [q](const auto& s) { return s.first == q; }), open.end());
   }
   seq_drain_spans(q);
   if (q->comm) {

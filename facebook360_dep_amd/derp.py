@@ -454,9 +454,10 @@ class Derp:
         self._ck(lib().derp_set_options(self.h, C.byref(self.opt)))
 
     def set_pyramid(self, sizes, width_full, height_full):
-        self.sizes = list(sizes)
+        sizes = list(sizes)
         self._ck(lib().derp_set_pyramid(self.h, len(sizes), _ints([s[0] for s in sizes]), _ints([s[1] for s in sizes]),
                                         width_full, height_full))
+        self.sizes = sizes  # (a refused call, e.g. with a SequenceRunner still open, leaves the geometry as it was)
 
     def _shape(self, level):
         w, h = self.sizes[level]

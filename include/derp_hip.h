@@ -80,7 +80,10 @@ const char* derp_last_error(const derp_ctx* ctx);
 int derp_set_options(derp_ctx* ctx, const derp_options* o);
 
 /* Pyramid geometry (getPyramidLevelSizes, Derp.cpp:72-99; widthFullSize/heightFullSize,
- * DerpCLI.cpp:212-214). Allocates the HBM-resident colour / disparity pyramid. */
+ * DerpCLI.cpp:212-214). Allocates the HBM-resident colour / disparity pyramid. May be called again with
+ * another geometry: the frame slots start again from one, and every table cached for a level is dropped.
+ * Fails, and changes nothing, while a derp_seq made on the context is open (derp_seq_destroy first): the
+ * sequence's buffers and slots have the old geometry's sizes. */
 int derp_set_pyramid(derp_ctx* ctx, int num_levels, const int* widths, const int* heights,
                      int width_full, int height_full);
 
