@@ -25,6 +25,7 @@
 #include "derp_mesh.h"
 #include "derp_points.h"
 #include "derp_render.h"
+#include "derp_stream.h"
 #include "derp_geometric.h"
 #include "derp_sweep.h"
 #include "derp_align.h"
@@ -1643,6 +1644,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
 #include "derp_render_api.h"
 #include "derp_rephoto_api.h"
 #include "derp_points_api.h"
+#include "derp_stream_api.h"
 #include "derp_mesh_api.h"
 #include "derp_geometric_api.h"
 #include "derp_sweep_api.h"

@@ -87,7 +87,7 @@ struct WorkLane {
 };
 
 // per tool family, defined in its derp_*_api.h and created by the family's first call that needs it
-struct SmrState; struct RephotoState; struct PointsState; struct MeshState; struct GcState; struct SweepState; struct AlignState; struct CoverageState;
+struct SmrState; struct RephotoState; struct PointsState; struct MeshState; struct GcState; struct SweepState; struct AlignState; struct CoverageState; struct StreamState;
 
 }  // namespace
 
@@ -196,6 +196,7 @@ struct derp_ctx {
   std::unique_ptr<SweepState> sweep;
   std::unique_ptr<AlignState> align;
   std::unique_ptr<CoverageState> coverage;
+  std::unique_ptr<StreamState> meshStream;
 };
 
 namespace {

@@ -174,6 +174,30 @@ int smr_prepare(derp_ctx* c, const derp_render_params& p, const std::vector<int>
   return 0;
 }
 
+// equirectFS over the fullscreen triangle on the cube texture `cube` (six E x E faces, GL rows) -> out [E][2 E]:
+// texVar = (pixel centre) / size, GL rows read bottom-up and not flipped, so output row r has
+// texVar.y = (r + 0.5) / H and lat = -(texVar.y - 0.5) pi: row 0 is the north pole. `tabs` is the caller's scratch.
+int smr_cube_to_equirect(derp_ctx* c, const float4* cube, int E, DevBuf& tabs, float4* out) {
+  const int W = 2 * E;
+  std::vector<float> tab((size_t)2 * (W + E));
+  for (int x = 0; x < W; ++x) {
+    const double lon = (1 - (x + 0.5) / W) * 2.0 * M_PI;
+    tab[2 * x] = (float)std::cos(lon);
+    tab[2 * x + 1] = (float)std::sin(lon);
+  }
+  for (int r = 0; r < E; ++r) {
+    const double lat = -((r + 0.5) / E - 0.5) * M_PI;
+    tab[2 * W + 2 * r] = (float)std::cos(lat);
+    tab[2 * W + 2 * r + 1] = (float)std::sin(lat);
+  }
+  ALLOC(c, tabs, tab.size() * 4);
+  HIPCHK(c, hipMemcpyAsync(tabs.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_smr_equirect, grid2d(W, E, 1, kBlk2d), kBlk2d, 0, c->stream, cube, E, tabs.as<float>(),
+                     tabs.as<float>() + 2 * W, W, E, out);
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // `tab` goes out of scope
+  return 0;
+}
+
 // one derp_render image into the device buffer `out` (CanopyScene::cubemap / equirect, the snapshot)
 int smr_image(derp_ctx* c, const derp_render_params& p, const uint8_t* include, float4* out) {
   SmrState& S = *c->smr;
@@ -201,26 +225,7 @@ int smr_image(derp_ctx* c, const derp_render_params& p, const uint8_t* include, 
   for (int face = 0; face < 6; ++face) {  // the cube texture keeps GL rows
     TRY(smr_view(c, smr_face_view(p, face, E), cams, p, 0, S.cube.as<float4>() + (size_t)face * E * E));
   }
-  // equirectFS over the fullscreen triangle: texVar = (pixel centre) / size, GL rows read bottom-up and not flipped,
-  // so output row r has texVar.y = (r + 0.5) / H and lat = -(texVar.y - 0.5) pi: row 0 is the north pole
-  const int W = 2 * E;
-  std::vector<float> tab((size_t)2 * (W + E));
-  for (int x = 0; x < W; ++x) {
-    const double lon = (1 - (x + 0.5) / W) * 2.0 * M_PI;
-    tab[2 * x] = (float)std::cos(lon);
-    tab[2 * x + 1] = (float)std::sin(lon);
-  }
-  for (int r = 0; r < E; ++r) {
-    const double lat = -((r + 0.5) / E - 0.5) * M_PI;
-    tab[2 * W + 2 * r] = (float)std::cos(lat);
-    tab[2 * W + 2 * r + 1] = (float)std::sin(lat);
-  }
-  ALLOC(c, S.tabs, tab.size() * 4);
-  HIPCHK(c, hipMemcpyAsync(S.tabs.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_smr_equirect, grid2d(W, E, 1, kBlk2d), kBlk2d, 0, c->stream, S.cube.as<float4>(), E, S.tabs.as<float>(),
-                     S.tabs.as<float>() + 2 * W, W, E, out);
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // `tab` goes out of scope
-  return 0;
+  return smr_cube_to_equirect(c, S.cube.as<float4>(), E, S.tabs, out);
 }
 
 // backgroundEquirect's nearest fetch (SimpleMeshRenderer.cpp:285-330) for a w x h image: the snapshot camera's ray

@@ -110,6 +110,13 @@ def render_params(kind="equirect", width=3072, height=None, position=(0, 0, 0), 
     return p
 
 
+def stream_srgb_table():
+    """sRGB -> linear of every 8-bit code, as derp_stream_upload decodes the colour texture -> f32 [256]"""
+    out = np.zeros(256, dtype=np.float32)
+    lib().derp_stream_srgb_table(out.ctypes.data_as(C.c_void_p))
+    return out
+
+
 def render_format_size(fmt, width, height):
     w, h = C.c_int(), C.c_int()
     if lib().derp_render_format_size(fmt.encode(), width, height, C.byref(w), C.byref(h)):
@@ -193,6 +200,11 @@ PROTOTYPES = {
     "derp_render_format_size": (_int, [_str, _int, _int, _ptr, _ptr]),
     "derp_render_format": (_int, [_ptr, _str, _view, _ptr, _ptr, _int, _int, _ptr]),
     "derp_render_vertices": (_int, [_ptr, _int, _f32, _ptr]),
+    "derp_stream_upload": (_int, [_ptr, _int, _ptr, _size, _ptr, _size, _ptr, _int, _int]),
+    "derp_stream_clear": (_int, [_ptr]),
+    "derp_stream_render": (_int, [_ptr, _view, _ptr, _f32, _ptr]),
+    "derp_stream_vertices": (_int, [_ptr, _int, _view, _int, _ptr]),
+    "derp_stream_srgb_table": (None, [_ptr]),
     "derp_export_points": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _f64, _int, _int, _ptr, _size, _ptr]),
     "derp_points_begin": (_int, [_ptr, _ptr, _ptr]),
     "derp_points_splat": (_int, [_ptr, _ptr, _size, _f64, _f64]),
@@ -747,6 +759,34 @@ class Derp:
         """camera `cam`'s mesh vertices after canopyVS's stereo stage (ipd 0: none) -> f32 [h, w, 4]."""
         out = np.zeros((shape[0], shape[1], 4), dtype=np.float32)
         self._ck(lib().derp_render_vertices(self.h, cam, ipd, _p(out)))
+        return out
+
+    # ---- MeshStreamRenderer (RigScene's mesh path): cameras = this context's destinations, at the colour's size
+    def stream_upload(self, cam, vtx, idx, rgba):
+        """camera `cam`'s mesh of one frame: vtx f32 [n, 3] (a, b, c), idx u32 [m] or [m / 3, 3], rgba u8 [h, w, 4]"""
+        vtx = np.ascontiguousarray(vtx, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1)
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+        assert rgba.ndim == 3 and rgba.shape[2] == 4
+        self._ck(lib().derp_stream_upload(self.h, cam, _p(vtx) if len(vtx) else None, len(vtx),
+                                          _p(idx) if len(idx) else None, len(idx), _p(rgba), rgba.shape[1], rgba.shape[0]))
+
+    def stream_clear(self):
+        self._ck(lib().derp_stream_clear(self.h))
+
+    def stream_render(self, params, include=None, fade=1.0):
+        """derp_stream_render of the uploaded meshes -> BGRA f32, the shapes of render()"""
+        h = params.height
+        w = {0: h, 1: 2 * h, 2: params.width}[params.kind]
+        out = np.zeros((6 * h if params.kind == 0 else h, w, 4), dtype=np.float32)
+        inc = None if include is None else np.ascontiguousarray(include, dtype=np.uint8)
+        self._ck(lib().derp_stream_render(self.h, C.byref(params), None if inc is None else _p(inc), fade, _p(out)))
+        return out
+
+    def stream_vertices(self, cam, count, params, face=0):
+        """clip coordinates of camera `cam`'s `count` uploaded vertices in params' view -> f32 [count, 4]"""
+        out = np.zeros((count, 4), dtype=np.float32)
+        self._ck(lib().derp_stream_vertices(self.h, cam, C.byref(params), face, _p(out)))
         return out
 
     # ---- conversion tools (source/conversion): cameras = this context's destinations, rescaled to the image size

@@ -287,6 +287,30 @@ int derp_render_format_size(const char* format, int width, int height, int* out_
 int derp_render_format(derp_ctx* ctx, const char* format, const derp_render_params* p, const float* background,
                        const float* background_equirect, int eq_w, int eq_h, float* out_bgra);
 int derp_render_vertices(derp_ctx* ctx, int cam, float ipd, float* out_xyzw);
+/* MeshStreamRenderer: the fused mesh stream (ConvertToBinary's .vtx / .idx / .rgba) rendered as the viewer renders it,
+ * without OpenGL — RigScene's mesh path (source/render/RigScene.cpp: cameraMeshVS :195-218, cameraFS :244-259,
+ * createDirection :869-885, renderSubframe :920-974, exponentialFS + updateAccumulation :281-292, 1009-1020, resolveFS
+ * :294-307, render :1071-1098) with indexed triangles, a near plane at 0.1 m that cuts a triangle instead of dropping
+ * it, GL_LESS with the earlier triangle kept on ties. Cameras = the destinations of derp_create as the rig file holds
+ * them (<rig>_fused.json: already at the colour's size). Outputs follow derp_render: BGRA float, NaN where nothing was
+ * rendered, the same CUBE / EQUIRECT / SNAPSHOT views and stacking.
+ * derp_stream_upload: camera `cam`'s mesh and colour of one frame: vtx = `vertices` x (a, b, c) floats, idx = `indices`
+ *   uint32 (three per triangle), rgba = [h][w][4] sRGB bytes. Refused on the host, before anything reaches the device:
+ *   indices not a multiple of 3, an index >= vertices (every index is read), (w, h) not the camera's resolution, a
+ *   null pointer with a non-zero count. A refused call leaves the scene as it was. An empty mesh renders nothing.
+ * derp_stream_clear: forgets every camera's upload.
+ * derp_stream_render: one image of the uploaded cameras include[s] != 0 (include NULL = all) for the view in p (kind,
+ *   width, height, position, forward, up, horizontal_fov, zero_nans; ipd and disparity_color must be 0; alpha_blend and
+ *   weight are not used: RigScene has one weight), rgb multiplied by `fade` (resolveFS).
+ * derp_stream_vertices: the vertex stage alone for p's view (`face` of the cube; ignored for a snapshot): clip
+ *   coordinates [vertices][4] (a test hook).
+ * derp_stream_srgb_table: host only; the sRGB -> linear value of every code, as the colour texture is decoded. */
+int derp_stream_upload(derp_ctx* ctx, int cam, const float* vtx, size_t vertices, const uint32_t* idx, size_t indices,
+                       const uint8_t* rgba, int w, int h);
+int derp_stream_clear(derp_ctx* ctx);
+int derp_stream_render(derp_ctx* ctx, const derp_render_params* p, const uint8_t* include, float fade, float* out_bgra);
+int derp_stream_vertices(derp_ctx* ctx, int cam, const derp_render_params* p, int face, float* out_clip_xyzw);
+void derp_stream_srgb_table(float* out256);
 /* ---- conversion tools at the depth stage's inputs and outputs (source/conversion) -------------------------------
  * The cameras are the destinations of derp_create (a --cameras-filtered rig is passed as both src and dst); `cam`
  * indexes them. Every call rescales the rig camera as the file holds it, Camera::rescale (Camera.cpp:217-223), to the
