@@ -595,10 +595,12 @@ __global__ void __launch_bounds__(kMeshBlock)
 }
 
 // The sorted keys are the feasible edges in (cost, face * 3 + edge) order (a stable sort of keys that went in by
-// ascending index), so an edge's position r is its rank. getThreshold's index over them:
+// ascending index), so an edge's position r is its rank. getThreshold's index over them (n > 0; the entries keep
+// strictness within [0, 1]):
 __device__ __forceinline__ unsigned long long mesh_threshold_key(const unsigned long long* __restrict__ skeys, unsigned long long n,
                                                                float strictness) {
-  return skeys[(int)(strictness * (float)(n - 1))];
+  const unsigned long long idx = (unsigned long long)(strictness * (float)(n - 1));  // (64 bits: no int to overflow)
+  return skeys[idx < n - 1 ? idx : n - 1];  // (float)(n - 1) rounds up past 2^24: the last rank at most
 }
 // claim: every candidate writes its rank to each face it touches; the smallest stays
 __global__ void __launch_bounds__(kMeshBlock)

@@ -339,6 +339,9 @@ int derp_mesh_simplify(derp_ctx* c, int num_faces_out, float strictness, int rem
   if (num_faces_out < 0) {
     return fail(c, "derp_mesh_simplify: a negative face budget");
   }
+  if (!(0 <= strictness && strictness <= 1)) {  // (NaN too) the threshold's rank would leave the feasible edges
+    return fail(c, "strictness must be between 0 and 1 (got %g)", (double)strictness);
+  }
   std::vector<double> V(m.nv * 3), planes, costs, vq;
   std::vector<int32_t> F(m.nf * 3);
   TRY(derp_mesh_download_f64(c, V.data(), F.data()));
@@ -373,6 +376,9 @@ int derp_mesh_simplify_parallel(derp_ctx* c, int num_faces_out, float strictness
   }
   if (num_faces_out < 0) {
     return fail(c, "derp_mesh_simplify_parallel: a negative face budget");
+  }
+  if (!(0 <= strictness && strictness <= 1)) {  // (NaN too) the threshold's rank would leave the feasible edges
+    return fail(c, "strictness must be between 0 and 1 (got %g)", (double)strictness);
   }
   HIPCHK(c, hipSetDevice(c->device));
   m.passes.clear();

@@ -113,7 +113,9 @@ struct Simplifier {
         errors[i * 3 + j] = faces[i].cost[j];
       }
     }
-    const int idxPerc = (int)(strictness * (float)(errors.size() - 1));  // float x size_t: a float product
+    // float x size_t: a float product; (float)(n - 1) rounds up past 2^24, where the reference reads past the end
+    // (narrowed to 64 bits, not to the reference's int: 3 x 2^31 costs fit the vector and not an int)
+    const size_t idxPerc = std::min((size_t)(strictness * (float)(errors.size() - 1)), errors.size() - 1);
     std::nth_element(errors.begin(), errors.begin() + idxPerc, errors.end());
     return errors[idxPerc];
   }
@@ -179,6 +181,9 @@ struct Simplifier {
     std::vector<int> common;
     while ((int)faces.size() > numFacesOut) {
       removeDeletedFaces();
+      if (faces.empty()) {  // the last collapse deleted what was left: getThreshold has no cost to index (the reference
+        break;              // indexes an empty vector here)
+      }
       assignFaceVertexes();
       if (iteration == 0) {
         identifyBoundaries();
@@ -319,6 +324,9 @@ extern "C" int derp_mesh_simplify_host(const double* vertices, size_t nv, const 
                                        int* stats) {
   if ((!vertices && nv) || (!faces && nf) || (!out_vertices && nv) || (!out_faces && nf) || !out_nv || !out_nf ||
       num_faces_out < 0 || nv > (size_t)INT32_MAX || nf > (size_t)INT32_MAX || !faces_in_range(faces, nf, nv)) {
+    return 1;
+  }
+  if (!(0 <= strictness && strictness <= 1)) {  // (NaN too) getThreshold's index would leave its vector
     return 1;
   }
   const bool given = face_planes && edge_costs && vertex_quadrics;

@@ -73,7 +73,7 @@ class ParallelSimplifier(R.Simplifier):
                 break
             # ---- step 3: the threshold, getThreshold's float product over the feasible costs only
             feasible.sort()
-            threshold = feasible[int(F32(strictness) * F32(len(feasible) - 1))][0]
+            threshold = feasible[R.threshold_index(strictness, len(feasible))][0]
             candidates = [k for k in feasible if k[0] <= threshold]
             # ---- step 4: winners = the candidates that hold the smallest key on every face they touch
             claim = {}

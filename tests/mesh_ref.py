@@ -236,6 +236,12 @@ def _sub(a, b):
     return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
 
 
+def threshold_index(strictness, n):
+    """getThreshold's index into n sorted costs: a float product, truncated; F32(n - 1) rounds up past 2^24, where the
+    reference reads past the end, so it is cut at the last cost"""
+    return min(int(F32(strictness) * F32(n - 1)), n - 1)
+
+
 class Simplifier:
     def __init__(self, V, F, setup_arrays, equi_error):
         planes, costs, vq = setup_arrays
@@ -311,7 +317,7 @@ class Simplifier:
     def threshold(self, strictness):  # getThreshold (:333-344)
         errors = [c for f in self.faces for c in f[4]]
         assert not any(c != c for c in errors), "a NaN cost: std::nth_element's result is not defined"
-        idx = int(F32(strictness) * F32(len(errors) - 1))
+        idx = threshold_index(strictness, len(errors))
         return sorted(errors)[idx]
 
     def normals_flipped(self, p, v0, v1):  # haveNormalsFlipped (:348-382)
@@ -354,6 +360,8 @@ class Simplifier:
         threshold, reason = 0.0, EXIT_BUDGET
         while len(self.faces) > num_faces_out:
             self.remove_deleted_faces()
+            if not self.faces:  # the last collapse deleted what was left: the reference indexes an empty vector here
+                break
             self.assign_face_vertexes()
             if iteration == 0:
                 self.identify_boundaries()

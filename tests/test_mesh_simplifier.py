@@ -40,6 +40,36 @@ def mesh_b(cam):
     return m["V"], m["F"]
 
 
+@pytest.fixture(scope="module")
+def mesh_flat(cam):
+    """tests/mesh_cases.py's flat 12 x 12 map: 4 distinct edge costs, negative, zero and positive"""
+    from tests import mesh_cases as M
+
+    m = M.build_case("flat_12")["want"]
+    assert len(m["F"]) == 242
+    return m["V"], m["F"]
+
+
+@pytest.fixture(scope="module")
+def mesh_triangle(cam):
+    """tests/mesh_cases.py's 2 x 2 map torn to one triangle"""
+    from tests import mesh_cases as M
+
+    m = M.build_case("single_triangle")["want"]
+    assert len(m["F"]) == 1 and len(m["V"]) == 3
+    return m["V"], m["F"]
+
+
+@pytest.fixture(scope="module")
+def mesh_quad(cam):
+    """tests/mesh_cases.py's whole 2 x 2 map: two faces with a common edge"""
+    from tests import mesh_cases as M
+
+    m = M.build_case("size_2x2")["want"]
+    assert len(m["F"]) == 2 and len(m["V"]) == 4
+    return m["V"], m["F"]
+
+
 # name -> (mesh fixture, budget, strictness, remove_boundary_edges, equi_error)
 CASES = {
     "a": ("mesh_a", 600, 0.2, False, True),
@@ -48,7 +78,17 @@ CASES = {
     "d_boundary": ("mesh_a", 600, 0.2, True, True),
     "d_not_equi": ("mesh_a", 600, 0.2, False, False),
     "d_both": ("mesh_a", 600, 0.2, True, False),
+    # both ends of getThreshold's index: the smallest cost and the largest
+    "s0_a": ("mesh_a", 600, 0.0, False, True),
+    "s1_a": ("mesh_a", 600, 1.0, False, True),
+    "s0_flat": ("mesh_flat", 40, 0.0, False, True),
+    "s1_flat": ("mesh_flat", 40, 1.0, False, True),
+    # the last collapse deletes what is left: no cost remains for the next pass's threshold
+    "to_nothing_triangle": ("mesh_triangle", 0, 0.2, True, True),
+    "to_nothing_quad": ("mesh_quad", 0, 0.2, True, True),
+    "to_one_of_quad": ("mesh_quad", 1, 1.0, True, True),
 }
+BAD_STRICTNESS = [1.5, -0.1, float("nan")]
 _want = {}
 
 
@@ -70,10 +110,19 @@ def check_properties(name, request, v, f, stats):
     elif name == "c":  # the loop is not entered
         assert stats == (0, R.EXIT_BUDGET)
         assert np.array_equal(v, V) and np.array_equal(f, F)
+    elif name in ("s0_a", "s0_flat"):  # the smallest cost is negative: it doubles to -inf and nothing collapses
+        assert stats[1] == R.EXIT_INFINITE_THRESHOLD and stats[0] > 3
+        assert np.array_equal(v, V) and np.array_equal(f, F)
+    elif name.startswith("to_"):  # one pass, one collapse, nothing left: empty arrays, not an index into no costs
+        assert stats == (1, R.EXIT_BUDGET) and v.shape == (0, 3) and f.shape == (0, 3)
+    elif name == "s1_flat":  # every edge is under the threshold; the boundary stays, so the budget is out of reach
+        assert stats[1] == R.EXIT_INFINITE_THRESHOLD and budget < len(f) < len(F)
     else:
         assert stats[1] == R.EXIT_BUDGET and stats[0] > 1
         assert budget - 2 <= len(f) <= budget  # a collapse removes at most two faces
         assert f.min() == 0 and f.max() == len(v) - 1 and len(np.unique(f)) == len(v)
+    if name == "s1_a":
+        assert stats != want("a", request)[2] and not np.array_equal(f, want("a", request)[1])
     if name == "d_boundary":
         assert len(v) != len(want("a", request)[0]) or not np.array_equal(v, want("a", request)[0])
 
@@ -118,6 +167,13 @@ def test_host_entries_refuse_bad_arguments(built, mesh_a):
         derp.mesh_setup_host(V, bad)
     with pytest.raises(derp.DerpError):
         derp.mesh_simplify_host(V, F, -1)
+    for strictness in BAD_STRICTNESS:  # getThreshold's index would leave its vector
+        with pytest.raises(derp.DerpError):
+            derp.mesh_simplify_host(V, F, 600, strictness)
+        with pytest.raises(derp.DerpError):
+            derp.mesh_simplify_host(V, F, 600, strictness, setup=derp.mesh_setup_host(V, F))
+    for strictness in (0.0, -0.0, 1.0):
+        derp.mesh_simplify_host(V, F, len(F), strictness)
 
 
 # ---------------------------------------------------------------- the same cases under the sanitizers
@@ -149,3 +205,14 @@ def test_sanitized_program_matches_the_restatement(harness, request, tmp_path, n
     wv, wf, wstats = want(name, request)
     assert (passes, reason) == wstats
     assert np.array_equal(f, wf) and v.tobytes() == wv.tobytes()
+
+
+@pytest.mark.parametrize("strictness", BAD_STRICTNESS)
+def test_sanitized_program_refuses_strictness_out_of_range(harness, mesh_a, tmp_path, strictness):
+    V, F = mesh_a
+    src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(src, "wb") as fh:
+        fh.write(struct.pack("<QQ", len(V), len(F)) + V.astype(np.float64).tobytes() + F.astype(np.int32).tobytes())
+    p = subprocess.run([harness, "run", src, dst, "600", repr(strictness), "0", "1"], capture_output=True, text=True, timeout=120)
+    assert "AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-1500:]
+    assert p.returncode == 1 and "bad arguments" in p.stderr and not os.path.exists(dst)
