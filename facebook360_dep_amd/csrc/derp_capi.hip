@@ -30,6 +30,7 @@
 #include "derp_sweep.h"
 #include "derp_align.h"
 #include "derp_coverage.h"
+#include "derp_preview.h"
 
 using namespace derp;
 
@@ -1651,6 +1652,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
 #include "derp_coverage_api.h"
 #include "derp_align_api.h"
 #include "derp_filters_api.h"
+#include "derp_preview_api.h"
 #include "derp_debug_api.h"
 #include "derp_sequence.h"
 #include "derp_isp.h"

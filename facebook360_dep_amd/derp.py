@@ -162,6 +162,12 @@ PROTOTYPES = {
     "derp_jpeg_encode": (_int, [_ptr, _int, _int, _int, _int, _ptr, _size, _ptr]),
     "derp_resize_area": (_int, [_ptr, _int, _ptr, _int, _int, _ptr, _int, _int]),
     "derp_generate_foreground_mask": (_int, [_ptr, _ptr, _ptr, _int, _int, _int, _f32, _int, _ptr]),
+    "derp_preview_variance_levels": (_int, [_f32, _f32, _int, _int, _f64, _ptr]),
+    "derp_preview_variance": (_int, [_ptr, _ptr, _int, _int, _ptr, _ptr, _int, _ptr, _ptr, _ptr]),
+    "derp_preview_foreground": (_int, [_ptr, _ptr, _ptr, _int, _int, _ptr, _int, _ptr, _int, _ptr, _int, _ptr, _ptr, _ptr]),
+    "derp_preview_keypoint_samples": (_int, [_cam, _cam, _f64, _f64, _ptr, _int, _ptr, _ptr, _ptr, _ptr]),
+    "derp_preview_keypoint_rect": (_int, [_f64, _f64, _int, _int, _int, _ptr]),
+    "derp_preview_keypoints": (_int, [_ptr, _int, _int, _ptr, _ptr, _ptr, _ptr]),
     "derp_process_level": (_int, [_ptr, _int]),
     "derp_process_pyramid": (_int, [_ptr, _int, _int]),
     "derp_synchronize": (_int, [_ptr]),
@@ -540,6 +546,52 @@ class Derp:
         self._ck(lib().derp_generate_foreground_mask(self.h, _p(template), _p(frame), w, h, blur_radius,
                                                      threshold, morph_closing_size, _p(out)))
         return out
+
+    # ---- tuning previews (ViewColorVarianceThresholds, ViewForegroundMaskThresholds)
+    def preview_variance(self, bgr, low_show, high_show, with_variance=False):
+        """n marked copies [n][h][w][3] of a BGR u16 image and counts [n][2] (blue, purple); the variance on request"""
+        bgr = np.ascontiguousarray(bgr, dtype=np.uint16)
+        low_show = np.ascontiguousarray(low_show, dtype=np.float32).reshape(-1)
+        high_show = np.ascontiguousarray(high_show, dtype=np.float32).reshape(-1)
+        assert bgr.ndim == 3 and bgr.shape[2] == 3 and low_show.size == high_show.size
+        h, w = bgr.shape[:2]
+        n = low_show.size
+        out = np.zeros((n, h, w, 3), dtype=np.uint16)
+        counts = np.zeros((n, 2), dtype=np.uint32)
+        var = np.zeros((h, w), dtype=np.float32) if with_variance else None
+        self._ck(lib().derp_preview_variance(self.h, _p(bgr), w, h, _p(low_show), _p(high_show), n, _p(out), _p(counts),
+                                             _p(var)))
+        return (out, counts, var) if with_variance else (out, counts)
+
+    def preview_foreground(self, template, frame, blur_radii=(1,), thresholds=(0.04,), closing_sizes=(4,)):
+        """overlays [nb*nt*nc][h][w][3], masks [..][h][w] and counts [..] of every (blur, threshold, closing), blur-major"""
+        template = np.ascontiguousarray(template, dtype=np.uint16)
+        frame = np.ascontiguousarray(frame, dtype=np.uint16)
+        assert template.shape == frame.shape and frame.ndim == 3 and frame.shape[2] == 3
+        blur = np.ascontiguousarray(blur_radii, dtype=np.int32).reshape(-1)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        close = np.ascontiguousarray(closing_sizes, dtype=np.int32).reshape(-1)
+        h, w = frame.shape[:2]
+        n = max(blur.size * thr.size * close.size, 1)
+        out = np.zeros((n, h, w, 3), dtype=np.uint16)
+        masks = np.zeros((n, h, w), dtype=np.uint8)
+        counts = np.zeros(n, dtype=np.uint32)
+        self._ck(lib().derp_preview_foreground(self.h, _p(template), _p(frame), w, h, _p(blur), blur.size, _p(thr), thr.size,
+                                               _p(close), close.size, _p(out), _p(masks), _p(counts)))
+        return out, masks, counts
+
+    def preview_keypoints(self, c0, c1, with_float=False, **params):
+        """GenerateKeypointProjections for the pair (c0, c1) after sweep_upload at scale 1 -> (u8 BGRA [h][w][4],
+        rectangles drawn), with the float blend in between on request"""
+        shapes = getattr(self, "_sweep_shapes", [])
+        if not 0 <= c0 < len(shapes):
+            raise DerpError("sweep_upload has not been called, or bad camera index %d" % c0)
+        p = keypoint_params(**params)
+        out = np.zeros(tuple(shapes[c0]) + (4,), dtype=np.uint8)
+        flt = np.zeros(tuple(shapes[c0]) + (4,), dtype=np.float32) if with_float else None
+        n = C.c_int(0)
+        self._ck(lib().derp_preview_keypoints(self.h, c0, c1, _p(p), _p(out), _p(flt), C.byref(n)))
+        return (out, flt, n.value) if with_float else (out, n.value)
 
     # ---- frame slots
     def set_frame_slots(self, n):
@@ -1231,6 +1283,44 @@ def gc_slice_count(cams, dst, small_size, disparity_step=0.5):
 def _host_ck(rc):
     if rc:
         raise DerpError(lib().derp_last_error(None).decode())
+
+
+def preview_variance_levels(var_low_max, var_high_max, low_slider, high_slider, scale=1.0):
+    """(varNoiseFloor, varHighThresh, varLowShow, varHighShow) of TrackVar::update, float32 [4]"""
+    out = np.zeros(4, dtype=np.float32)
+    _host_ck(lib().derp_preview_variance_levels(var_low_max, var_high_max, int(low_slider), int(high_slider), scale, _p(out)))
+    return out
+
+
+def keypoint_params(length_stride=0.125, height_stride=0.125, depth_min=1.0, depth_max=100.0, depth_samples=1000.0,
+                    search_overlap=0.25, search_radius=100):
+    """the seven doubles of derp_preview_keypoint*, at the reference's defaults"""
+    return np.array([length_stride, height_stride, depth_min, depth_max, depth_samples, search_overlap, search_radius],
+                    dtype=np.float64)
+
+
+def preview_keypoint_samples(cam_point, cam_into, px, py, max_out=4096, **params):
+    """-> (indices int32 [n], disparities f64 [n], boxes f32 [n][4] as x, y, width, height) of the accepted samples"""
+    p = keypoint_params(**params)
+    idx, disp = np.zeros(max_out, np.int32), np.zeros(max_out, np.float64)
+    boxes = np.zeros((max_out, 4), np.float32)
+    n = C.c_int(0)
+    _host_ck(lib().derp_preview_keypoint_samples(C.byref(camera_desc(cam_point)), C.byref(camera_desc(cam_into)), float(px),
+                                                 float(py), _p(p), max_out, _p(idx), _p(disp), _p(boxes), C.byref(n)))
+    k = min(n.value, max_out)
+    return idx[:k], disp[:k], boxes[:k]
+
+
+def preview_keypoint_rect(px, py, search_radius, w, h):
+    """(x0, y0, x1, y1), inclusive and clipped, of the rectangle drawn for a projected point"""
+    out = np.zeros(4, np.int32)
+    _host_ck(lib().derp_preview_keypoint_rect(float(px), float(py), int(search_radius), int(w), int(h), _p(out)))
+    return tuple(int(v) for v in out)
+
+
+def preview_foreground_threshold(slider):
+    """threshold = threshMax * slider / 100 with threshMax = 1.0f (ViewForegroundMaskThresholds.cpp:72, :141)"""
+    return np.float32(1.0) * np.float32(int(slider)) / np.float32(100)
 
 
 def sweep_overlap_disparities(num_depths, min_depth_m=1, max_depth_m=10):

@@ -543,6 +543,54 @@ int derp_align_setup(derp_ctx* ctx, const derp_camera_desc* red_ref, int n_red, 
                      int n_green, const derp_camera_desc* blue_ref, int n_blue);
 int derp_align_maps(derp_ctx* ctx, int cam, float* red_xy, float* blue_xy);
 int derp_align_frame(derp_ctx* ctx, const uint16_t* const* bgr, const int* img_w, const int* img_h, uint16_t* const* out);
+/* ---- The tuning previews (source/render/ViewColorVarianceThresholds.cpp, ViewForegroundMaskThresholds.cpp): the images
+ * the reference's trackbar windows show, for lists of slider positions instead of a window ----
+ * Images are interleaved BGR uint16; the context's cameras are not read. One call renders at most 256 settings, and
+ * a call whose device buffers exceed 4 GiB (DERP_PREVIEW_BUDGET_MB overrides it) is refused by name.
+ * derp_preview_variance_levels: TrackVar::update's thresholds (ViewColorVarianceThresholds.cpp:69-73) for slider positions
+ *   0..100 and scale = width / cols (1 when --width=0), in the reference's fp32 order -> levels4 = {varNoiseFloor,
+ *   varHighThresh, varLowShow, varHighShow}. Host only, no context and no device; a refusal leaves its text in
+ *   derp_last_error(NULL).
+ * derp_preview_variance: computeImageVariance (DerpUtil.cpp:214-237, the level loop's kernel) once, then n marked copies
+ *   of the image [n][h][w][3]: variance < low_show[k] -> (65535, 0, 0), variance > high_show[k] -> (65535, 0, 65535),
+ *   both strict. counts[2k] / counts[2k + 1] = the blue / purple pixels of image k. out_variance ([h][w] float) may be
+ *   NULL.
+ * derp_preview_foreground: for every (blur, threshold, closing), blur-major, the mask derp_generate_foreground_mask
+ *   answers for it, laid over the frame as cv::addWeighted(frame, 1.0, green where the mask is set, 0.5, 0) does on
+ *   CV_16UC3: G = min(65535, rint(g + 32767.5)) half to even inside the mask, everything else unchanged.
+ *   out_bgr16 [nb*nt*nc][h][w][3], out_mask [nb*nt*nc][h][w] 0 / 1 or NULL, counts[nb*nt*nc] = the mask's set pixels.
+ *   The limits on the image and the radius are derp_generate_foreground_mask's, refused with its message.
+ * GenerateKeypointProjections (source/render/GenerateKeypointProjections.cpp:57-104): where a grid of points of camera c1
+ * lands in camera c0 over the depth range. params = {length_stride, height_stride, depth_min, depth_max, depth_samples,
+ * search_overlap, search_radius} (seven doubles; the strides positive and finite, search_radius a whole number >= 0,
+ * depth_samples >= 2, 0 < depth_min <= depth_max, else refused by name).
+ * derp_preview_keypoint_samples: getNextDepthSample + computeBox (FeatureMatcher.cpp:116-133, 186-207) for the pixel
+ *   (px, py) of cam_point, boxes in cam_into, both at their own resolutions: the accepted sample indices, their
+ *   disparities and cv::Rect2f boxes (x, y, width, height). *n = how many were accepted, of which min(*n, max_out) are
+ *   written. Host only, no context and no device; a refusal leaves its text in derp_last_error(NULL).
+ * derp_preview_keypoint_rect: the filled cv::rectangle of one projected point: corners cvRound(p - 0.5 -+ search_radius)
+ *   (half to even), both inclusive, clipped to w x h -> rect4 = {x0, y0, x1, y1}; x1 < x0 or y1 < y0: nothing of it is
+ *   inside. Host only.
+ * derp_preview_keypoints: the pair (c0, c1) of the context's destinations after derp_sweep_upload at scale 1: the
+ *   rectangles (corners cvRound(p - 0.5 -+ search_radius), inclusive, clipped, a later one over an earlier one in the
+ *   reference's loop order) in the grid point's colour (height_frac, width_frac, 1 - height_frac, 1), blended as
+ *   image * 1.0f + rectangles * 0.6f + 0.0f. out_bgra8 [h][w][4] = 255.0f * blend as the rig preview tools convert it;
+ *   out_float [h][w][4] the blend itself, or NULL; *n_rects = the rectangles drawn, those clipped away included (a
+ *   camera whose resolution exceeds the first camera's sees points beyond the image). More than 2^20 grid points or
+ *   2^20 rectangles of one pair are refused by name. */
+int derp_preview_variance_levels(float var_low_max, float var_high_max, int low_slider, int high_slider, double scale,
+                                 float* levels4);
+int derp_preview_variance(derp_ctx* ctx, const uint16_t* bgr16, int w, int h, const float* low_show,
+                          const float* high_show, int n, uint16_t* out_bgr16, uint32_t* counts, float* out_variance);
+int derp_preview_foreground(derp_ctx* ctx, const uint16_t* template_bgr16, const uint16_t* frame_bgr16, int w, int h,
+                            const int* blur, int nb, const float* threshold, int nt, const int* closing, int nc,
+                            uint16_t* out_bgr16, uint8_t* out_mask, uint32_t* counts);
+int derp_preview_keypoint_samples(const derp_camera_desc* cam_point, const derp_camera_desc* cam_into, double px, double py,
+                                  const double* params, int max_out, int* indices, double* disparities, float* boxes4,
+                                  int* n);
+int derp_preview_keypoint_rect(double px, double py, int search_radius, int w, int h, int* rect4);
+int derp_preview_keypoints(derp_ctx* ctx, int c0, int c1, const double* params, uint8_t* out_bgra8, float* out_float,
+                           int* n_rects);
 /* Host only, no context and no device (derp_simplify.cpp); non-zero = bad arguments (null pointer, an index out of
  * range, a negative budget, more than 2^31 - 1 vertices or faces).
  * derp_mesh_setup_host: computeInitialQuadrics over plain arrays: vertices f64 [nv][3], faces i32 [nf][3] -> the three
