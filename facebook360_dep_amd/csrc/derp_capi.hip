@@ -409,15 +409,37 @@ size_t table_bytes_per_dst(const derp_ctx* c, int W, int H, bool withInverse) {
                                (DERP_RANDOM_TILED ? tiled_plane(W, H) * sizeof(ushort4) : 0));
 }
 
-int compute_fov_and_masks(derp_ctx* c, int level) {
+// The table budget -> the destination batch: how many of the D destinations' projection tables fit `budget` bytes.
+// Batches need stored inverse warps for the sources outside them, so a level that does not fit whole pays
+// `perWithInverse` bytes per destination. DB = 0: bad sizes, or not even one destination fits. Pure arithmetic.
+TableBatch plan_table_batch(int D, size_t perNoInverse, size_t perWithInverse, bool inverseNeededAnyway, size_t budget) {
+  if (D < 1 || perNoInverse == 0 || perWithInverse == 0) {
+    return {0, false};
+  }
+  const bool inv = inverseNeededAnyway || budget / perNoInverse < (size_t)D;
+  const int DB = (int)std::min<size_t>(D, budget / (inv ? perWithInverse : perNoInverse));
+  if (DB < 1) {
+    return {0, inv};
+  }
+  // equal-sized batches: 24 destinations under a 23-destination budget run as 12 + 12, not 23 + 1
+  const int batches = (D + DB - 1) / DB;
+  return {(D + batches - 1) / batches, inv};
+}
+
+// only the frame that opens a level honours opt.rebuild_warp_tables, for the warps and the FOV masks alike
+bool rebuilds_tables(const derp_ctx* c, LevelUse use) {
+  return use == LevelUse::Open && c->opt.rebuild_warp_tables;
+}
+
+int compute_fov_and_masks(derp_ctx* c, int level, LevelUse use) {
   const int W = c->LW[level], H = c->LH[level];
   const size_t n = (size_t)W * H;
   {
     Span sp(c, ST_FOV, level);
     // the FOV masks depend on the rig and the level size only, like the projection warps, and follow their rule
-    // (rebuild_warp_tables, warpCachedLevel): the first frame of a level builds them into the context's buffer, the
+    // (rebuilds_tables, warpCachedLevel): the first frame of a level builds them into the context's buffer, the
     // other frames of the level, on the work lanes too, read them there. fov & fg stays per frame.
-    if (c->opt.rebuild_warp_tables || c->fovCachedLevel != level) {
+    if (rebuilds_tables(c, use) || c->fovCachedLevel != level) {
       hipLaunchKernelGGL(k_fov_mask, grid2d(W, H, c->D, kBlk2d), kBlk2d, 0, c->stream, c->camsDst.as<Cam>(), W, H,
                          c->fovMask.as<uint8_t>());
       KCHECK(c);
@@ -781,19 +803,71 @@ int check_level(derp_ctx* c, int level) {
   return 0;
 }
 
-// Level set-up: what DerpCLI does before processLevel (DerpCLI.cpp:221-303)
-int level_begin(derp_ctx* c, int level, bool buildAllTables) {
+// a level the level loop can run: present, 3 x 3 at least, on a rig within the cost kernels' source limit
+int check_level_runs(derp_ctx* c, int level) {
   TRY(check_level(c, level));
   if (c->S - 1 > kMaxSrc) {
     return fail(c, "too many source cameras (%d > %d)", c->S, kMaxSrc + 1);
   }
+  if (c->LW[level] < 3 || c->LH[level] < 3) {
+    return fail(c, "level %d is too small (%dx%d)", level, c->LW[level], c->LH[level]);
+  }
+  return 0;
+}
+
+// What the frames of a pass over `level` share: the table budget -> the destination batch, and the warp buffers at that
+// batch. It depends on the rig, the level size and the free memory only. The one place that asks the runtime for the
+// free memory and the one place that allocates a buffer the work lanes share; it enqueues nothing.
+int level_open(derp_ctx* c, int level) {
+  TRY(check_level_runs(c, level));
+  ++c->plan.decisions;
+  c->plan.level = -1;  // until the new plan stands
+  const int W = c->LW[level], H = c->LH[level];
+  const size_t n = (size_t)W * H;
+  // When the buffers already hold every destination's tables of this level (the steady state of a sequence: same
+  // levels frame after frame) there is nothing to ask the runtime.
+  // (the inverse-warp table only exists when a batch holds a source that is not one of its destinations)
+  const bool invAll = batch_needs_inverse_warps(c, 0, c->D);
+  TableBatch batch{c->D, invAll};
+  const size_t wpAll = (size_t)(W + 2 * kPadW) * (H + 2 * kPadW) * (c->S - 1) * c->D * sizeof(float2);
+  const size_t cpAll = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC) * (c->S - 1) * c->D * sizeof(ushort4);
+  const size_t ipAll = n * (c->S - 1) * c->D * sizeof(float2);
+  const bool resident = c->projWarp.bytes >= wpAll && c->w.projColor.bytes >= cpAll && c->w.projBias.bytes >= cpAll &&
+      (!invAll || c->projWarpInv.bytes >= ipAll) && !getenv("DERP_TABLE_BUDGET_GB") &&
+      (!DERP_RANDOM_TILED || c->w.projColorT.bytes >= tiled_plane(W, H) * (c->S - 1) * c->D * sizeof(ushort4));
+  if (!resident) {
+    size_t freeB = 0, totalB = 0;
+    HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
+    size_t budget = freeB + c->projWarp.bytes + c->w.projColor.bytes + c->w.projBias.bytes + c->projWarpInv.bytes + c->w.projColorT.bytes;
+    if (const char* e = getenv("DERP_TABLE_BUDGET_GB")) {
+      budget = std::min<size_t>(budget, (size_t)(atof(e) * (1ull << 30)));
+    } else {
+      budget = (size_t)(budget * 0.85);
+    }
+    const size_t perInverse = table_bytes_per_dst(c, W, H, true);
+    batch = plan_table_batch(c->D, table_bytes_per_dst(c, W, H, false), perInverse, invAll, budget);
+    if (batch.DB < 1) {
+      return fail(c, "projection tables for one destination (%zu bytes) exceed the table budget (%zu bytes)", perInverse, budget);
+    }
+  }
+  ALLOC(c, c->projWarp, (size_t)batch.DB * (c->S - 1) * (W + 2 * kPadW) * (H + 2 * kPadW) * sizeof(float2));
+  if (batch.storeInverse) {
+    ALLOC(c, c->projWarpInv, (size_t)batch.DB * (c->S - 1) * n * sizeof(float2));
+  }
+  c->plan.level = level;
+  c->plan.DB = batch.DB;
+  c->plan.storeInverse = batch.storeInverse;
+  return 0;
+}
+
+// One frame's set-up of a level whose plan stands: what DerpCLI does before processLevel (DerpCLI.cpp:221-303), on this
+// work set. `seedOptional`: the stage-level API starts a level without the level above's disparity.
+int frame_level_begin(derp_ctx* c, int level, LevelUse use, bool seedOptional = false) {
+  TRY(check_level_runs(c, level));
   c->cur = level;
   const int W = c->LW[level], H = c->LH[level];
   const size_t n = (size_t)W * H;
-  if (W < 3 || H < 3) {
-    return fail(c, "level %d is too small (%dx%d)", level, W, H);
-  }
-  TRY(compute_fov_and_masks(c, level));
+  TRY(compute_fov_and_masks(c, level, use));
   {
     // the variance and the own colour bias come from one pass over the colour plane: the pass reports under `variance`,
     // and `own_bias` reads 0
@@ -811,7 +885,7 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   if (c->w.mismatchMaskHeld) {
     HIPCHK(c, hipMemsetAsync(c->w.mismatchMask.p, 0, n * c->D, c->stream));
   }
-  if (level < c->numLevels - 1 && !c->frame().haveDisp[level + 1] && !buildAllTables) {
+  if (level < c->numLevels - 1 && !c->frame().haveDisp[level + 1] && !seedOptional) {
     return fail(c, "Missing disparity of level %d needed to start level %d", level + 1, level);
   }
   if (level < c->numLevels - 1 && c->frame().haveDisp[level + 1]) {
@@ -836,65 +910,15 @@ int level_begin(derp_ctx* c, int level, bool buildAllTables) {
   } else {
     HIPCHK(c, hipMemsetAsync(c->w.disparity.p, 0, n * c->D * sizeof(float), c->stream));
   }
-  // table budget -> dst batch. When the buffers already hold every destination's tables of this level (the
-  // steady state of a sequence: same levels frame after frame) there is nothing to ask the runtime.
-  // (the inverse-warp table only exists when a batch holds a source that is not one of its destinations)
-  const bool invAll = batch_needs_inverse_warps(c, 0, c->D);
-  size_t per = table_bytes_per_dst(c, W, H, invAll);
-  int DB = c->D;
-  bool needInv = invAll;
-  {
-    const size_t wpAll = (size_t)(W + 2 * kPadW) * (H + 2 * kPadW) * (c->S - 1) * c->D * sizeof(float2);
-    const size_t cpAll = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC) * (c->S - 1) * c->D * sizeof(ushort4);
-    const size_t ipAll = (size_t)W * H * (c->S - 1) * c->D * sizeof(float2);
-    const bool resident = c->projWarp.bytes >= wpAll && c->w.projColor.bytes >= cpAll && c->w.projBias.bytes >= cpAll &&
-        (!invAll || c->projWarpInv.bytes >= ipAll) && !getenv("DERP_TABLE_BUDGET_GB") &&
-        (!DERP_RANDOM_TILED || c->w.projColorT.bytes >= tiled_plane(W, H) * (c->S - 1) * c->D * sizeof(ushort4));
-    if (!resident) {
-      size_t freeB = 0, totalB = 0;
-      HIPCHK(c, hipMemGetInfo(&freeB, &totalB));
-      size_t budget = freeB + c->projWarp.bytes + c->w.projColor.bytes + c->w.projBias.bytes + c->projWarpInv.bytes + c->w.projColorT.bytes;
-      if (const char* e = getenv("DERP_TABLE_BUDGET_GB")) {
-        budget = std::min<size_t>(budget, (size_t)(atof(e) * (1ull << 30)));
-      } else {
-        budget = (size_t)(budget * 0.85);
-      }
-      DB = (int)std::min<size_t>((size_t)c->D, budget / std::max<size_t>(per, 1));
-      if (DB < c->D && !needInv) {  // batches: the sources outside a batch need stored inverse warps
-        needInv = true;
-        per = table_bytes_per_dst(c, W, H, true);
-        DB = (int)std::min<size_t>((size_t)c->D, budget / std::max<size_t>(per, 1));
-      }
-      if (DB < 1) {
-        return fail(c, "projection tables for one destination (%zu bytes) exceed the table budget (%zu bytes)", per, budget);
-      }
-      // equal-sized batches: 24 destinations under a 23-destination budget run as 12 + 12, not 23 + 1
-      const int batches = (c->D + DB - 1) / DB;
-      DB = (c->D + batches - 1) / batches;
-    }
-  }
-  c->DB = DB;
-  const size_t wp = (size_t)(W + 2 * kPadW) * (H + 2 * kPadW), cp = (size_t)(W + 2 * kPadC) * (H + 2 * kPadC);
-  ALLOC(c, c->projWarp, (size_t)DB * (c->S - 1) * wp * sizeof(float2));
-  ALLOC(c, c->w.projColor, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
-  ALLOC(c, c->w.projBias, (size_t)DB * (c->S - 1) * cp * sizeof(ushort4));
-  if (needInv) {
-    ALLOC(c, c->projWarpInv, (size_t)DB * (c->S - 1) * n * sizeof(float2));
-  }
+  // this work set's own colour tables, at the plan's batch
+  const size_t tables = (size_t)c->plan.DB * (c->S - 1);
+  ALLOC(c, c->w.projColor, tables * (W + 2 * kPadC) * (H + 2 * kPadC) * sizeof(ushort4));
+  ALLOC(c, c->w.projBias, tables * (W + 2 * kPadC) * (H + 2 * kPadC) * sizeof(ushort4));
   if (DERP_RANDOM_TILED) {
-    ALLOC(c, c->w.projColorT, (size_t)DB * (c->S - 1) * tiled_plane(W, H) * sizeof(ushort4));
+    ALLOC(c, c->w.projColorT, tables * tiled_plane(W, H) * sizeof(ushort4));
   }
   c->tablesValid = false;
   c->randomRanThisLevel = false;
-  if (buildAllTables) {
-    if (DB < c->D) {
-      return fail(c, "stage-level API needs all destinations' tables resident (batch %d < %d)", DB, c->D);
-    }
-    if (c->opt.rebuild_warp_tables || c->warpCachedLevel != level) {
-      TRY(build_warp(c, 0, c->D));
-      c->warpCachedLevel = level;
-    }
-  }
   return 0;
 }
 
@@ -906,12 +930,33 @@ int level_end(derp_ctx* c) {
   return 0;
 }
 
-int process_level(derp_ctx* c, int level) {
-  TRY(level_begin(c, level, false));
-  for (int d0 = 0; d0 < c->D; d0 += c->DB) {
-    const int nd = std::min(c->DB, c->D - d0);
-    const bool single = (c->DB == c->D);
-    if (!single || c->opt.rebuild_warp_tables || c->warpCachedLevel != level) {
+// A work lane's frame, whose kernels overlap other frames', may only Join, and only a level that the first frame of the
+// pass left complete: then nothing process_level reaches asks for free memory, grows a shared buffer or builds warps.
+int check_lane_join(derp_ctx* c, int level, LevelUse use) {
+  const LevelPlan& p = c->plan;
+  if (use != LevelUse::Join || p.level != level || p.DB != c->D || c->warpCachedLevel != level || c->fovCachedLevel != level) {
+    return fail(c, "work lanes need every destination's tables in one batch (level %d: %d of %d)", level,
+                p.level == level ? p.DB : 0, c->D);
+  }
+  return 0;
+}
+
+// processLevel of the selected frame. In turn on the context's own work set, a Join whose plan is not for this level
+// (something else used the context in between) opens the level itself; on a lane check_lane_join has passed
+// (process_level_on_lane).
+int process_level(derp_ctx* c, int level, LevelUse use) {
+  if (use == LevelUse::Join && c->plan.level != level) {
+    use = LevelUse::Open;
+  }
+  if (use == LevelUse::Open) {
+    TRY(level_open(c, level));
+  }
+  TRY(frame_level_begin(c, level, use));
+  const int DB = c->plan.DB;
+  for (int d0 = 0; d0 < c->D; d0 += DB) {
+    const int nd = std::min(DB, c->D - d0);
+    const bool single = (DB == c->D);
+    if (!single || rebuilds_tables(c, use) || c->warpCachedLevel != level) {
       TRY(build_warp(c, d0, nd));
       c->warpCachedLevel = single ? level : -1;
     }
@@ -1028,18 +1073,19 @@ int lanes_prepare(derp_ctx* c, int count, size_t n) {
 }
 
 // processLevel of the frame in slot `slot` on lane `i` (i < 0: on the context's own working set and stream). The lane's
-// stream first waits for c->laneReady.
-int process_level_on_lane(derp_ctx* c, int i, int slot, int level) {
+// stream first waits for c->laneReady; a frame that may not join is refused before anything is enqueued there.
+int process_level_on_lane(derp_ctx* c, int i, int slot, int level, LevelUse use) {
   if (i < 0) {
     TRY(select_frame(c, slot));
-    return process_level(c, level);
+    return process_level(c, level, use);
   }
+  TRY(check_lane_join(c, level, use));
   HIPCHK(c, hipStreamWaitEvent(c->lanes[i]->stream, c->laneReady, 0));
   lane_swap(c, i);
   c->activeLane = i;
   int rc = select_frame(c, slot);
   if (!rc) {
-    rc = process_level(c, level);
+    rc = process_level(c, level, use);
   }
   if (!rc && hipEventRecord(c->lanes[i]->done, c->stream) != hipSuccess) {
     rc = fail(c, "work lane: hipEventRecord failed");
@@ -1292,6 +1338,7 @@ int derp_set_pyramid(derp_ctx* c, int num_levels, const int* widths, const int* 
   TRY(alloc_work_set(c, c->w, nmax));
   ALLOC(c, c->fovMask, nmax * c->D);
   c->cur = -1;
+  c->plan.level = -1;
   c->warpCachedLevel = -1;
   c->fovCachedLevel = -1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1417,7 +1464,7 @@ int derp_upload_disparity(derp_ctx* c, int level, int d, const float* disp) {
 
 int derp_process_level(derp_ctx* c, int level) {
   TRY(use_device(c));
-  return process_level(c, level);
+  return process_level(c, level, LevelUse::Open);
 }
 
 int derp_process_pyramid(derp_ctx* c, int level_start, int level_end_) {
@@ -1426,7 +1473,7 @@ int derp_process_pyramid(derp_ctx* c, int level_start, int level_end_) {
     return fail(c, "Check failed: level_start >= level_end (%d vs %d)", level_start, level_end_);
   }
   for (int level = level_start; level >= level_end_; --level) {
-    TRY(process_level(c, level));
+    TRY(process_level(c, level, LevelUse::Open));
   }
   return 0;
 }
@@ -1478,7 +1525,16 @@ int derp_download_cost(derp_ctx* c, int d, float* cost, float* confidence) {
 // ---- stage-level API ----
 int derp_level_begin(derp_ctx* c, int level) {
   TRY(use_device(c));
-  return level_begin(c, level, true);
+  TRY(level_open(c, level));
+  TRY(frame_level_begin(c, level, LevelUse::Open, true));
+  if (c->plan.DB < c->D) {
+    return fail(c, "stage-level API needs all destinations' tables resident (batch %d < %d)", c->plan.DB, c->D);
+  }
+  if (c->opt.rebuild_warp_tables || c->warpCachedLevel != level) {
+    TRY(build_warp(c, 0, c->D));
+    c->warpCachedLevel = level;
+  }
+  return 0;
 }
 int derp_stage_reproject_colors(derp_ctx* c) {
   TRY(need_current(c, false));
@@ -1633,7 +1689,7 @@ int derp_download_mismatch_mask(derp_ctx* c, int d, uint8_t* out) {
     return fail(c, "bad destination index / null output");
   }
   const size_t n = npx(c, c->cur);
-  if (!c->w.mismatchMaskHeld) {  // no mismatch stage at this level: nothing was flagged (level_begin)
+  if (!c->w.mismatchMaskHeld) {  // no mismatch stage at this level: nothing was flagged (frame_level_begin)
     memset(out, 0, n);
     return 0;
   }

@@ -80,6 +80,22 @@ struct FramePyramid {
   std::vector<char> haveBg, haveDisp;
 };
 
+// What the frames of one pass over a level share (level_open): the destination batch that fits the table budget and
+// whether inverse warps are stored. The first frame of the pass makes it, the others, the work lanes' too, only read it.
+struct LevelPlan {
+  int level = -1;  // the level it was made for (-1: none)
+  int DB = 0;
+  bool storeInverse = false;
+  int decisions = 0;  // level_open calls since derp_create (derp_debug_level_plan)
+};
+struct TableBatch {  // plan_table_batch's answer
+  int DB;
+  bool storeInverse;
+};
+// A frame's place in a pass over a level. Open: the first frame, and every direct call: it makes the level's plan and
+// honours opt.rebuild_warp_tables. Join: a later frame: it reuses the plan and what Open left in the shared tables.
+enum class LevelUse { Open, Join };
+
 struct WorkLane {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
@@ -128,7 +144,7 @@ struct derp_ctx {
 
   // ---- the working level
   int cur = -1;
-  int DB = 0;  // dst batch that fits the table budget
+  LevelPlan plan;
   WorkSet w;             // the per-frame working set in use: the context's own, or a lane's while its frame runs
   DevBuf temporalCarry;  // accumulators of a temporal window longer than one launch holds
   DevBuf projWarp, projWarpInv;

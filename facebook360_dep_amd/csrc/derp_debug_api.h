@@ -349,6 +349,16 @@ int derp_debug_block_trace(derp_ctx* c, const char* stage, int level, uint64_t* 
   return fail(c, "this library records no block trace: build it with -DDERP_BLOCK_TRACE=1 (tools/block_trace.py)");
 #endif
 }
+int derp_debug_level_plan(derp_ctx* c, int32_t* out) {
+  if (!c || !out) {
+    return fail(c, "bad arguments");
+  }
+  out[0] = c->plan.level;
+  out[1] = c->plan.DB;
+  out[2] = c->plan.storeInverse;
+  out[3] = c->plan.decisions;
+  return 0;
+}
 int derp_device_memory(derp_ctx* c, uint64_t* free_bytes, uint64_t* total_bytes) {
   TRY(use_device(c));
   size_t f = 0, t = 0;
@@ -400,4 +410,15 @@ int derp_host_cost_tile_map(int tiles, int bands, int rot, int per_block, int* o
     }
   }
   return blocks;
+}
+// the table budget -> the destination batch, as level_open decides it (plan_table_batch); 1: refused
+int derp_host_table_batch(int n_dst, uint64_t bytes_no_inverse, uint64_t bytes_with_inverse, int inverse_needed,
+                          uint64_t budget_bytes, int* batch, int* store_inverse) {
+  const TableBatch b = plan_table_batch(n_dst, bytes_no_inverse, bytes_with_inverse, inverse_needed != 0, budget_bytes);
+  if (!batch || !store_inverse || b.DB < 1) {
+    return 1;
+  }
+  *batch = b.DB;
+  *store_inverse = b.storeInverse;
+  return 0;
 }

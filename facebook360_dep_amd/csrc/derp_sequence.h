@@ -877,7 +877,7 @@ int stream_in_level(derp_seq* q, int k, int level, bool forCompute) {
 }
 
 // processLevel(level) of owned frame k in out-of-core mode: stream in, compute, stream the raw level out
-int stream_compute_frame(derp_seq* q, int level, int k) {
+int stream_compute_frame(derp_seq* q, int level, int k, LevelUse use) {
   derp_ctx* c = q->c;
   const int slot = k % q->nSlots;
   TRY(select_frame(c, slot));
@@ -902,7 +902,7 @@ int stream_compute_frame(derp_seq* q, int level, int k) {
       }
     }
   }
-  TRY(process_level(c, level));
+  TRY(process_level(c, level, use));
   const size_t bytes = npx(c, level) * c->D * sizeof(float);
   float* out = q->opt.do_temporal_filter ? q->hostRaw[k] : q->hostDisp[k][level];
   HIPCHK(c, hipMemcpyAsync(out, c->frame().disp[level].p, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -1137,6 +1137,28 @@ int derp_seq_exchange_inputs(derp_seq* q) {
   return 0;
 }
 
+namespace {
+// The next frame of a pass over `level`: the first one opens the level, the others join it. The projection warps depend
+// on the rig and the level size only (precomputeProjections, Derp.cpp:955-976): the first frame builds them (always,
+// when rebuild_warp_tables asks for the reference's per-invocation rebuild), the other frames of the level reuse them.
+LevelUse seq_enter_level(derp_seq* q, int level) {
+  if (q->computeLevel != level) {
+    q->computeLevel = level;
+    q->computedFrames = 0;
+    q->levelReady = -1;
+  }
+  return q->computedFrames == 0 ? LevelUse::Open : LevelUse::Join;
+}
+// owned frame k holds its raw level; the last one completes the pass
+void seq_frame_computed(derp_seq* q, int level, int k) {
+  q->computedAt[k] = level;
+  q->filteredAt[k] = -1;
+  if (++q->computedFrames >= (int)q->owned.size()) {
+    q->levelReady = level;
+  }
+}
+}  // namespace
+
 int derp_seq_level_compute_frame(derp_seq* q, int level, int frame) {
   if (!q) {
     return 1;
@@ -1148,32 +1170,14 @@ int derp_seq_level_compute_frame(derp_seq* q, int level, int frame) {
   if (k < 0) {
     return fail(c, "frame %d is not owned by rank %d", frame, q->rank);
   }
-  if (q->computeLevel != level) {
-    q->computeLevel = level;
-    q->computedFrames = 0;
-    q->levelReady = -1;
-  }
-  // the projection warps depend on the rig and the level size only (precomputeProjections, Derp.cpp:955-976):
-  // the first frame of the level builds them (always, when rebuild_warp_tables asks for the reference's
-  // per-invocation rebuild), the other frames of the level reuse them
-  const int rebuild = c->opt.rebuild_warp_tables;
-  c->opt.rebuild_warp_tables = q->computedFrames == 0 ? rebuild : 0;
-  int rc;
+  const LevelUse use = seq_enter_level(q, level);
   if (q->streaming) {
-    rc = stream_compute_frame(q, level, k);
+    TRY(stream_compute_frame(q, level, k, use));
   } else {
-    rc = select_frame(c, k);
-    if (!rc) {
-      rc = process_level(c, level);
-    }
+    TRY(select_frame(c, k));
+    TRY(process_level(c, level, use));
   }
-  c->opt.rebuild_warp_tables = rebuild;
-  TRY(rc);
-  q->computedAt[k] = level;
-  q->filteredAt[k] = -1;
-  if (++q->computedFrames >= (int)q->owned.size()) {
-    q->levelReady = level;
-  }
+  seq_frame_computed(q, level, k);
   return 0;
 }
 
@@ -1203,16 +1207,8 @@ int derp_seq_level_provided_frame(derp_seq* q, int level, int frame) {
     return fail(c, "frame %d has no complete level %d disparity (derp_seq_upload_disparity of every destination first)", frame, level);
   }
   q->uploaded[slotLevel] = 0;
-  if (q->computeLevel != level) {
-    q->computeLevel = level;
-    q->computedFrames = 0;
-    q->levelReady = -1;
-  }
-  q->computedAt[k] = level;
-  q->filteredAt[k] = -1;
-  if (++q->computedFrames >= (int)q->owned.size()) {
-    q->levelReady = level;
-  }
+  seq_enter_level(q, level);
+  seq_frame_computed(q, level, k);
   return 0;
 }
 
@@ -1251,30 +1247,18 @@ int derp_seq_level_compute(derp_seq* q, int level) {
     Span wall(c, ST_LANES, level);
     for (int k = 0; k < (int)q->owned.size(); ++k) {
       const int lane = k == 0 ? -1 : (k - 1) % lanes;
-      if (q->computeLevel != level) {
-        q->computeLevel = level;
-        q->computedFrames = 0;
-        q->levelReady = -1;
-      }
-      const int rebuild = c->opt.rebuild_warp_tables;
-      c->opt.rebuild_warp_tables = k == 0 ? rebuild : 0;
-      const int rc = process_level_on_lane(c, lane, k, level);
-      c->opt.rebuild_warp_tables = rebuild;
-      TRY(rc);
+      TRY(process_level_on_lane(c, lane, k, level, seq_enter_level(q, level)));
       if (k == 0) {
-        if (c->DB != c->D) {
-          return fail(c, "work lanes need every destination's tables in one batch (level %d: %d of %d)", level, c->DB, c->D);
+        if (c->plan.DB != c->D) {
+          return fail(c, "work lanes need every destination's tables in one batch (level %d: %d of %d)", level, c->plan.DB, c->D);
         }
         HIPCHK(c, hipEventRecord(c->laneReady, c->stream));
       }
-      q->computedAt[k] = level;
-      q->filteredAt[k] = -1;
-      ++q->computedFrames;
+      seq_frame_computed(q, level, k);
     }
     for (int i = 0; i < lanes; ++i) {
       HIPCHK(c, hipStreamWaitEvent(c->stream, c->lanes[i]->done, 0));
     }
-    q->levelReady = level;
     return 0;
   }
   for (int t : q->owned) {

@@ -192,6 +192,7 @@ PROTOTYPES = {
     "derp_debug_sees": (_int, [_ptr, _int, _ptr, _size, _ptr]),
     "derp_debug_expf": (_int, [_ptr, _int, _ptr, _ptr, _size]),
     "derp_debug_block_trace": (_int, [_ptr, _str, _int, _ptr, _size, _ptr, _ptr]),
+    "derp_debug_level_plan": (_int, [_ptr, _ptr]),
     "derp_download_mismatch_mask": (_int, [_ptr, _int, _ptr]),
     "derp_layer_disparities": (_int, [_ptr, _ptr, _ptr, _size, _ptr]),
     "derp_ssim": (_int, [_ptr, _ptr, _ptr, _int, _int, _int, _f32, _f32, _f32, _ptr]),
@@ -348,6 +349,7 @@ PROTOTYPES = {
     "derp_host_nth_element_pairs": (_int, [_ptr, _int, _int]),
     "derp_host_minstd_uniform": (_f32, [_int, _u64, _f32, _f32]),
     "derp_host_cost_tile_map": (_int, [_int, _int, _int, _int, _ptr, _int]),
+    "derp_host_table_batch": (_int, [_int, _u64, _u64, _int, _u64, _ptr, _ptr]),
 }
 EXPORTS = list(PROTOTYPES)  # every symbol include/derp_hip.h declares
 
@@ -1152,6 +1154,13 @@ class Derp:
         self._ck(lib().derp_debug_block_trace(self.h, stage.encode(), level, _p(out), out.size, C.byref(gx), C.byref(gy)))
         return out
 
+    def debug_level_plan(self):
+        """What the frames of the level opened last share -> dict(level, batch, store_inverse, decisions); `decisions`
+        counts the levels opened since the context was made"""
+        out = np.zeros(4, dtype=np.int32)
+        self._ck(lib().derp_debug_level_plan(self.h, _p(out)))
+        return dict(level=int(out[0]), batch=int(out[1]), store_inverse=int(out[2]), decisions=int(out[3]))
+
     def device_memory(self):
         """-> (free, total) bytes of HBM right now"""
         f, t = C.c_uint64(), C.c_uint64()
@@ -1529,6 +1538,15 @@ def host_cost_tile_map(tiles, bands, rot, per_block):
     if blocks <= 0:
         raise ValueError("bad tile map arguments")
     return out[:blocks * per_block].reshape(blocks, per_block)
+
+
+def host_table_batch(n_dst, bytes_no_inverse, bytes_with_inverse, inverse_needed, budget_bytes):
+    """The table budget -> (destinations per batch, inverse warps stored) of a level (host arithmetic, no GPU)."""
+    batch, inverse = C.c_int(), C.c_int()
+    if lib().derp_host_table_batch(n_dst, bytes_no_inverse, bytes_with_inverse, int(bool(inverse_needed)), budget_bytes,
+                                   C.byref(batch), C.byref(inverse)):
+        raise ValueError("bad arguments, or not even one destination's tables fit the budget")
+    return batch.value, bool(inverse.value)
 
 
 def average_score(score, mask):

@@ -217,6 +217,10 @@ int derp_debug_expf(derp_ctx* ctx, int mode, const float* x, float* out, size_t 
  * random-proposal ("random_proposals") / ping-pong ("ping_pong") launch of `level`, out[(y * grid_x + x) * 2 ..]; with
  * out = NULL or too small a capacity (in uint64s) only the grid is returned. Fails in the shipped library. */
 int derp_debug_block_trace(derp_ctx* ctx, const char* stage, int level, uint64_t* out, size_t capacity, int* grid_x, int* grid_y);
+/* what the frames of the level opened last share: out[0 .. 3] = {the level (-1: none), the destination batch that fits
+ * the table budget, 1 if inverse warps are stored, how many times a level was opened since derp_create}. A level is
+ * opened once per pass over it: by its first frame, and by every direct derp_process_level / derp_level_begin. */
+int derp_debug_level_plan(derp_ctx* ctx, int32_t* out);
 
 /* mismatch mask of the level processed last (dstMismatchedDisparityMask, PyramidLevel.h:332-338) */
 int derp_download_mismatch_mask(derp_ctx* ctx, int dst, uint8_t* out);
@@ -922,6 +926,12 @@ float derp_host_minstd_uniform(int seed, uint64_t draw_index, float a, float b);
  * (the destination index) and `per_block` tiles per block (1, 2, 4). Returns the number of blocks of the grid (a tile
  * index at or past `tiles` is padding), or 0 on bad arguments or when `capacity` ints do not hold the map. */
 int derp_host_cost_tile_map(int tiles, int bands, int rot, int per_block, int* out, int capacity);
+/* the table budget -> the destination batch of a level: how many of `n_dst` destinations' projection tables fit
+ * `budget_bytes` at `bytes_no_inverse` each, or at `bytes_with_inverse` each when inverse warps are stored: always if
+ * `inverse_needed`, otherwise as soon as the level runs in batches. *batch is the size of the equal-sized batches,
+ * *store_inverse whether inverse warps are stored. Returns 1 on bad arguments or when not even one destination fits. */
+int derp_host_table_batch(int n_dst, uint64_t bytes_no_inverse, uint64_t bytes_with_inverse, int inverse_needed,
+                          uint64_t budget_bytes, int* batch, int* store_inverse);
 
 #ifdef __cplusplus
 }
